@@ -14,6 +14,12 @@ Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, the trail
 syrk on v_mfma_f64_16x16x4_f64: algorithmic flops per launch = 256 m (m+1) for a trailing
 matrix of order m (N^3/3 in total), time from hipEvents around every launch
 on the library's stream inside the timed region.
+
+A plain run sets up, warms up, times --steps steps and prints the line with what those steps
+measured.  --full adds, on one GPU, the measurements with runs of their own: the headline
+through GPInterpolation (`api_route_ms`), configs[0..2] (`configs_measured`) and the CPU
+baseline (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step returned
+(dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -40,7 +46,7 @@ FP64_MFMA_PEAK_TFLOPS = 78.6     # MI355X fp64 matrix peak
 def cpu_baseline(n_s, m_s, n_headline):
     """The reference's own SciPy call sequence (oracle/cpu_reference_path.py) on the host cores, protocol of
     BASELINE.md section 3: BLAS threads = the fastest of {cgroup quota, physical cores, half, quarter, 16, 32}
-    on a dpotrf probe, 1 warm-up + 5 timed passes (fewer, never below 3, only if a 90 s budget is spent), median per phase; sample =
+    (none above the thread count the BLAS started with) on a dpotrf probe, 1 warm-up + 5 timed passes (fewer, never below 3, only if a 90 s budget is spent), median per phase; sample =
     configs[1] in full (N=8192 / M=32768).  `extrapolated_n65536` scales the measured phases to the headline size
     (dpotrf by N^3, pair loops by N^2 and M N) and is labelled as such."""
     from oracle import cpu_reference_path as R
@@ -52,7 +58,13 @@ def cpu_baseline(n_s, m_s, n_headline):
     cand = {phys, max(phys // 2, 1), max(phys // 4, 1), 16, 32}
     if host["cgroup_quota"]:
         cand.add(max(int(round(host["cgroup_quota"])), 1))
-    cand = sorted(c for c in cand if 1 <= c <= host["logical"])
+    # OpenBLAS segfaults when a thread limit above the count it started with (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else
+    # the CPU count) is set: no candidate goes past that count
+    from threadpoolctl import threadpool_info
+    started = [int(p["num_threads"]) for p in threadpool_info() if p.get("user_api") == "blas"]
+    cap = min(started + [host["logical"]])
+    cand.add(cap)
+    cand = sorted(c for c in cand if 1 <= c <= cap)
     threads, probe = R.pick_blas_threads(cand)
     med, npass = R.timed_passes(X, y - y.mean(), y_err, Xs, iL, 1.0, threads)
     blas = "unknown BLAS"
@@ -397,6 +409,23 @@ def collective_backend():
     return rec
 
 
+DUMP_MAX_ELEMS = 1 << 20       # per array: 8 MB of float64 (+ 8 MB of sample positions); 32 MB at most for alpha + predictions
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each array as d/<name>.npy in float64, for comparing two builds output for output.  An array of more
+    than DUMP_MAX_ELEMS elements is written as a fixed, seeded sample of that many (ascending positions, the same for every
+    run of the same size) with the positions beside it in d/<name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(20240613).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -404,10 +433,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--ntrain", dest="n", type=int, default=65536, help="training points (default: headline 65536)")
     ap.add_argument("--mpredict", dest="m", type=int, default=0, help="prediction points (default 4 n)")
-    ap.add_argument("--cpu-sample", type=int, default=8192, help="N of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=8192, help="N of the CPU-baseline sample of --full (0 = skip)")
     ap.add_argument("--meanify", action="store_true", help="configs[4]'s recipe: mean-function table (KNN-4) under the field")
     ap.add_argument("--api", action="store_true", help="one GPU: step through GPInterpolation too (always so with --gpus > 1)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the configs[1] / configs[2] measurements of the one-GPU line")
+    ap.add_argument("--no-configs", action="store_true", help="skip the API-route and configs[0..2] measurements of --full")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the headline, also the API route, configs[0..2] and the CPU baseline (minutes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     n = args.n
     m = args.m or 4 * n
@@ -505,12 +538,13 @@ def main():
         import treegp_amd
         gp = treegp_amd.GPInterpolation(kernel=headline_kernel_string(), optimizer="none", normalize=True, white_noise=0.0,
                                         average_fits=fits, backend="dist" if use_dist else "single")
+        last = {}
 
         def step(acc):
             t0 = time.perf_counter()
             gp.initialize(X, y, y_err)
             t1 = time.perf_counter()
-            gp.predict(Xs)
+            last["y_pred"] = gp.predict(Xs)
             t2 = time.perf_counter()
             acc["api_initialize_ms"] = acc.get("api_initialize_ms", 0.0) + (t1 - t0) * 1e3
             acc["api_predict_ms"] = acc.get("api_predict_ms", 0.0) + (t2 - t1) * 1e3
@@ -532,6 +566,13 @@ def main():
         step(acc)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        if not api:
+            # what the C-ABI calls hand their caller: alpha and the predictions (of y - mean) on the device, two scalars
+            outputs = {"alpha": da.to_array(n), "y_pred": dys.to_array(m), "logdet": [ld.value], "y_dot_alpha": [yd.value]}
+        else:
+            outputs = {"y_pred": np.asarray(last["y_pred"])}
+        dump_outputs(args.dump_outputs, outputs)
     per_rank = None
     if use_dist:
         import torch
@@ -659,15 +700,16 @@ def main():
                                        # of 256 CUs x 4 SIMDs x 16 lanes at 2.4 GHz
                                        "valu_issue_frac_at_2p4ghz": m_rank * n * K / (acc["predict_ms"] * 1e-3) * 16.4 / (256 * 4 * 16 * 2.4e9)}
             out["phases_ms_per_step"] = {k: acc[k] / K for k in ("kbuild_ms", "chol_ms", "trsv_ms", "predict_ms", "syrk_ms")}
-        if not use_dist and not api and not args.no_configs:
+        # --full: what the headline does not need, each with runs of its own after the timed steps (a plain run stops here)
+        if args.full and not use_dist and not api and not args.no_configs:
             # the same workloads once more through the drop-in API on this one GPU (host buffers in, NumPy out): what the
             # N > 1 lines, which always step through GPInterpolation, are to be compared with.  Medians of 5 passes after a
             # warm-up; `host_tax_ms` = wall minus the library's own device phases of the same calls (api_route).
             out["api_route_ms"] = {"headline": api_route(X, y, y_err, Xs, headline_kernel_string(), passes=5)}
             out["api_route_ms_per_step_one_gpu"] = {k: out["api_route_ms"]["headline"][k] for k in ("initialize", "predict", "total")}
-        if not use_dist and not args.no_configs:
+        if args.full and not use_dist and not args.no_configs:
             out["configs_measured"] = configs_measured(lib, ctx, ops, _lib)
-        if not use_dist and args.cpu_sample > 0:
+        if args.full and not use_dist and args.cpu_sample > 0:
             out["cpu_baseline"] = cpu_baseline(args.cpu_sample, 4 * args.cpu_sample, n)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -369,7 +369,7 @@ def test_bench_meanify_recipe_through_api_rehearsal():
 
 
 def test_bench_line_schema_single_gpu():
-    """The one JSON line of `python bench.py` (contract of the round driver): keys, units and the roofline / cpu_baseline
+    """The one JSON line of `python bench.py --full` (contract of the round driver): keys, units and the roofline / cpu_baseline
     objects, on a small instance of the workload (the CPU leg on a 1024-point sample)."""
     import json
     import subprocess
@@ -379,7 +379,7 @@ def test_bench_line_schema_single_gpu():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--ntrain", "24576",
-                        "--cpu-sample", "1024"], env=env, capture_output=True, text=True, timeout=900)
+                        "--cpu-sample", "1024", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -432,6 +432,50 @@ def test_bench_line_schema_single_gpu():
     assert "TreeCorr absent" in c2b["pair_binning"] and "restatement" in c2b["pair_binning"]
     assert any(k.startswith("extrapolated_n") for k in cb)
     np.testing.assert_allclose(out["value"], (24576 + 4 * 24576) / (out["ms_per_step"] * 1e-3), rtol=1e-9)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` (no --full) times --steps steps and prints the headline without the measurements of
+    --full; --dump-outputs writes what the last timed step returned, on the C-ABI path and through GPInterpolation (--api),
+    and both agree with the same solve run here."""
+    import json
+    import subprocess
+    from treegp_amd import ops
+    from treegp_amd.synthetic import star_field
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    n = 4096
+    lines = {}
+    for mode in ("capi", "api"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--ntrain", str(n),
+               "--dump-outputs", str(tmp_path / mode)] + (["--api"] if mode == "api" else [])
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        ls = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(ls) == 1, r.stdout[-2000:]
+        lines[mode] = out = json.loads(ls[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"] == "f64"
+        assert out["unit"] == "points/s" and out["higher_is_better"] is True
+        np.testing.assert_allclose(out["value"], 5 * n / (out["ms_per_step"] * 1e-3), rtol=1e-9)
+        for key in ("api_route_ms", "api_route_ms_per_step_one_gpu", "configs_measured", "cpu_baseline"):
+            assert key not in out, key
+    assert "roofline" in lines["capi"] and lines["api"]["config"]["through_api"] is True
+    spec, X, y, y_err, Xs = _problem(n, 4 * n, seed=20240613)
+    alpha, logdet, ydota, _ = ops.gp_solve(spec, X, y, y_err)
+    yp = ops.gp_predict(spec, X, alpha, Xs)
+    got = {name: np.load(str(tmp_path / "capi" / (name + ".npy"))) for name in ("alpha", "y_pred", "logdet", "y_dot_alpha")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["alpha"].shape == (n,) and got["y_pred"].shape == (4 * n,) and got["logdet"].shape == (1,)
+    np.testing.assert_allclose(got["alpha"], alpha, rtol=0, atol=1e-10 * np.abs(alpha).max())
+    np.testing.assert_allclose(got["y_pred"], yp, rtol=0, atol=1e-10 * np.abs(yp).max())
+    np.testing.assert_allclose(got["logdet"][0], logdet, rtol=1e-12)
+    np.testing.assert_allclose(got["y_dot_alpha"][0], ydota, rtol=1e-10)
+    ymean = star_field(n, 4 * n)[1].mean()
+    yp_api = np.load(str(tmp_path / "api" / "y_pred.npy"))
+    assert yp_api.dtype == np.float64 and yp_api.shape == (4 * n,)
+    np.testing.assert_allclose(yp_api, yp + ymean, rtol=0, atol=1e-9 * np.abs(yp + ymean).max())
 
 
 def test_bench_multi_gpu_path_on_rccl_world_of_one():

@@ -213,6 +213,29 @@ def test_bench_self_launches_its_ranks_and_fails_loudly_without_a_gpu():
     assert not any(line.startswith("{") for line in r.stdout.splitlines())
 
 
+def test_bench_dump_outputs_writes_float64_and_a_fixed_sample_of_large_arrays(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float64; one above the size cap as the same seeded sample in
+    every run (positions beside it in <name>_index.npy), so that two builds compare element for element."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    big = np.arange(5000, dtype=np.float32) * 0.5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": np.arange(7.0), "scalar": [1.25]})
+    for d in ("a", "b"):
+        assert sorted(os.listdir(str(tmp_path / d))) == ["big.npy", "big_index.npy", "scalar.npy", "small.npy"]
+    small, scalar = np.load(str(tmp_path / "a" / "small.npy")), np.load(str(tmp_path / "a" / "scalar.npy"))
+    assert small.dtype == np.float64 and np.array_equal(small, np.arange(7.0)) and scalar.tolist() == [1.25]
+    va, ia = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "a" / "big_index.npy"))
+    vb, ib = np.load(str(tmp_path / "b" / "big.npy")), np.load(str(tmp_path / "b" / "big_index.npy"))
+    assert va.dtype == np.float64 and ia.dtype == np.float64 and va.shape == (1000,)
+    assert np.array_equal(ia, ib) and np.array_equal(va, vb)
+    assert np.all(np.diff(ia) > 0) and len(np.unique(ia)) == 1000
+    assert np.array_equal(va, big.astype(np.float64)[ia.astype(np.int64)])
+
+
 class _FakeMinuit2(object):
     """The slice of iminuit 2.x's API that two_pcf.py:157-168 of the reference (and robust_2dfit._run_migrad here) uses:
     Minuit(fcn, start), .migrad(), .parameters, .params[name].value, .accurate.  The minimiser behind it is SciPy's."""

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python3 bench.py > $O/${TAG}_bench_n65536.json 2> $O/${TAG}_bench.err
+python3 bench.py --full > $O/${TAG}_bench_n65536.json 2> $O/${TAG}_bench.err
 echo "bench done"
 python3 tools/kernel_bench.py > $O/${TAG}_kernel_bench.jsonl 2> /dev/null
 python3 tools/trsv_bench.py 1000 2300 4096 8192 16384 32768 65536 2> /dev/null | grep '^{' > $O/${TAG}_trsv_bench.jsonl
