@@ -242,6 +242,8 @@ int tgp_d_potrs(tgp_ctx *ctx, const double *d_A, const double *d_W, int64_t Np, 
 int tgp_d_potrs_multi(tgp_ctx *ctx, const double *d_A, const double *d_W, int64_t Np, double *d_B, int nrhs);
 /* unpack the lower triangle into a dense (n, n) row-major host matrix (upper part zero) */
 int tgp_d_unpack_lower(tgp_ctx *ctx, const double *d_A, int64_t Np, int64_t n, double *out);
+/* read-only view of a kept (or borrowed) factor: its packed panels, inverted blocks and Np; changes nothing */
+int tgp_factor_device(tgp_ctx *ctx, const tgp_factor *f, const double **d_A, const double **d_W, int64_t *Np);
 /* ---- multi-GPU tier (one process per GPU; driver: treegp_amd/dist.py) ------------------------
  * Row-block-cyclic over 256-row blocks with the deal reflected every G blocks: round q = b / G gives
  * rank g block q G + g when q is even and q G + (G-1-g) when q is odd, so that the lower triangle's

@@ -369,6 +369,14 @@ int tgp_d_unpack_lower(tgp_ctx *ctx, const double *d_A, int64_t Np, int64_t n, d
     return 0;
 }
 
+int tgp_factor_device(tgp_ctx *ctx, const tgp_factor *f, const double **d_A, const double **d_W, int64_t *Np) {
+    TGP_ARG(f && d_A && d_W && Np);
+    *d_A = f->d_A;
+    *d_W = f->d_W;
+    *Np = f->Np;
+    return 0;
+}
+
 // ---- S2 -------------------------------------------------------------------------------------
 // What follows the K build, shared by the parametrised kernels (tgp_d_gp_solve) and the caller-built matrix
 // (tgp_d_gp_solve_dense): factorise the packed matrix in the context's cache, solve, log-determinant, y . alpha.
