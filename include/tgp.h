@@ -8,6 +8,7 @@
  *   S2  cholesky + cho_solve (+ logdet)  treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
+ *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
  *   S6  binned_statistic_2d              treegp/meanify.py:76-107
@@ -69,7 +70,7 @@ int tgp_device_count(void);
  * [0] K build  [1] Cholesky total  [2] triangular solves  [3] predict  [4] pair binning
  * [5] trailing-update (syrk) kernel time summed  [6] number of trailing-update launches
  * [7] trailing-update flops (sum over launches)  [8] K-build bytes written
- * [9] result transfer of tgp_gp_predict_cov ([3] is then its device compute time)
+ * [9] result transfer of tgp_gp_predict_cov / tgp_gp_predict_var ([3] is then its device compute time)
  * [10] triangular sweeps over L inside [2]: 2 = forward + backward, 1 = backward only (the forward substitution
  *      rode along with the factorisation, inside [1]), 0 = none (likelihood only, right-hand side as a matrix row) */
 #define TGP_NTIMINGS 11
@@ -133,6 +134,17 @@ int tgp_gp_predict_cov(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const d
  * (treegp/gp_interp.py:177,191 for kernel trees that go through tgp_gp_solve_dense)              */
 int tgp_gp_predict_cov_dense(tgp_ctx *ctx, tgp_factor *f, const double *HT, const double *Kss,
                              int64_t m, double *cov);
+
+/* ---- S3c: posterior variance, the diagonal of S3b without the (m, m) matrix -------------------
+ * Every caller of predict(X, return_cov=True) in the reference keeps only np.diag(y_cov) (its tests, e.g.
+ * tests/test_gp_interp.py:51-52).  var (m) = diag(k(Xs,Xs) - HT K^-1 HT^T) from a kept factor; any m (processed in
+ * chunks of query rows: TGP_VAR_CHUNK rows, rounded up to 256, overrides the default; the result does not depend on
+ * the chunk).  Not clamped at zero.  Timings as tgp_gp_predict_cov: [3] device compute, [9] result transfer.      */
+int tgp_gp_predict_var(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n,
+                       const double *Xs, int64_t m, double *var);
+/* the same with HT = kernel(X2, Y=X1) (m, n) and kss = kernel.diag(X2) (m) evaluated by the caller */
+int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const double *HT, const double *kss,
+                             int64_t m, double *var);
 
 /* ---- S2d: gradient of the log marginal likelihood from a kept factor and its alpha ---------
  * (the reference's optimiser passes no jac, treegp/log_likelihood.py:57 -- this is what a caller who wants one

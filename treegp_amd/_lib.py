@@ -70,6 +70,8 @@ SIGNATURES = {
     "tgp_d_gp_solve_dense": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _dp, _dp, C.POINTER(_vp)]),
     "tgp_factor_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "tgp_gp_predict_cov_dense": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
+    "tgp_gp_predict_var": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _i64, _vp]),
+    "tgp_gp_predict_var_dense": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "tgp_gp_loglik_grad": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp]),
     "tgp_d_gp_solve_grad": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _dp, _dp, _vp]),
     "tgp_d_unpack_lower": (C.c_int, [_vp, _vp, _i64, _i64, _vp]),

@@ -1,4 +1,5 @@
 // Posterior covariance (seam S3b): cov = k(Xs, Xs) - HT (K + D)^-1 HT^T  (treegp/gp_interp.py:184-192)
+// and its diagonal alone, the posterior variance (seam S3c, further down)
 // from the factor kept by tgp_gp_solve.  With Bt = HT L^-T (M x N) the result is
 // Kss - Bt Bt^T, which reuses the factor instead of factorising a second time (the reference's
 // own comment at gp_interp.py:189) and keeps the subtraction symmetric.
@@ -102,20 +103,23 @@ __global__ __launch_bounds__(256, 2) void cov_syrk_kernel(double *Cpm, const dou
 }  // namespace
 
 namespace {
-// geometry + scratch shared by the two entry points
+// geometry + scratch shared by the entry points.  Covariance (var_rows == 0): Bt is Mp x Np, the result d_C Mp x Mp.
+// Variance (var_rows > 0, seam S3c): Bt holds one chunk of Mp = var_rows query rows and there is no d_C; d_v and d_kss are Mp
+// doubles each (the chunk's variances, the caller's k(x_i, x_i) of the dense route).  d_Xs holds all m query points either way.
 struct CovPlan {
     int64_t n, m, Np, Mp;
     int nP, nPm;
-    double *d_X, *d_Xs, *d_Bt, *d_C;
+    double *d_X, *d_Xs, *d_Bt, *d_C, *d_v, *d_kss;
 };
-int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan *pl) {
+int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan *pl, int64_t var_rows = 0) {
     pl->n = f->n; pl->m = m; pl->Np = f->Np;
     pl->nP = (int)(pl->Np / TGP_PW);
-    pl->Mp = (m + TGP_PW - 1) / TGP_PW * TGP_PW;                  // 256: the covariance uses the panel layout too
+    pl->Mp = var_rows ? var_rows : (m + TGP_PW - 1) / TGP_PW * TGP_PW;   // 256: the covariance uses the panel layout too
     pl->nPm = (int)(pl->Mp / TGP_PW);
-    TGP_ARG(pl->Mp <= 65535);
+    TGP_ARG(pl->Mp <= 65535 && pl->Mp % TGP_PW == 0);
     auto rup = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t need = (coords ? rup(2 * pl->n * 8) + rup(2 * m * 8) : 0) + rup((size_t)pl->Mp * pl->Np * 8) + rup((size_t)pl->Mp * pl->Mp * 8);
+    const size_t tail = var_rows ? 2 * rup((size_t)pl->Mp * 8) : rup((size_t)pl->Mp * pl->Mp * 8);
+    const size_t need = (coords ? rup(2 * pl->n * 8) + rup(2 * m * 8) : 0) + rup((size_t)pl->Mp * pl->Np * 8) + tail;
     int rc = tgp_ensure_scratch(ctx, need);
     if (rc) return rc;
     char *base = (char *)ctx->scratch;
@@ -124,7 +128,9 @@ int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan 
     pl->d_X = coords ? take(2 * pl->n * 8) : nullptr;
     pl->d_Xs = coords ? take(2 * m * 8) : nullptr;
     pl->d_Bt = take((size_t)pl->Mp * pl->Np * 8);
-    pl->d_C = take((size_t)pl->Mp * pl->Mp * 8);
+    pl->d_C = var_rows ? nullptr : take((size_t)pl->Mp * pl->Mp * 8);
+    pl->d_v = var_rows ? take((size_t)pl->Mp * 8) : nullptr;
+    pl->d_kss = var_rows ? take((size_t)pl->Mp * 8) : nullptr;
     return 0;
 }
 // Bt <- Bt L^-T by block substitution.  `tri`: Bt starts as the identity (m == n), so at the step that eliminates columns
@@ -239,6 +245,136 @@ extern "C" int tgp_gp_predict_cov_dense(tgp_ctx *ctx, tgp_factor *f, const doubl
                                  (size_t)w * 8, (size_t)m, hipMemcpyHostToDevice, st));
     }
     return cov_finish(ctx, f, pl, cov);
+}
+
+// ---- posterior variance (seam S3c): var_i = k(x_i, x_i) - |Bt_i|^2, the diagonal of the covariance above without forming it ----
+// Callers of the reference take np.diag of the covariance and nothing else.  The query points go through in chunks of Mc rows:
+// HT of the chunk into Bt, the same substitution as the covariance (cov_substitute, unchanged), then one pass of
+// var_rows_kernel over the chunk's Bt.  No M x M buffer, so m is not bounded by the covariance's 65 535.  Rows of Bt do not
+// depend on the rows around them and var_rows_kernel sums in a fixed order, so the result does not depend on Mc.
+#ifndef TGP_VAR_CHUNK_DEFAULT
+#define TGP_VAR_CHUNK_DEFAULT 16384   // rows per chunk (LAB_NOTES.md: 4096 - 32 768 measured)
+#endif
+#define TGP_VAR_CHUNK_MAX 65280       // largest multiple of 256 that the row grids of cov.hip accept (<= 65 535)
+namespace {
+// one wave per query row: each lane squares 2 + 2 doubles of every 256-wide panel row (two 16-byte loads, 1 KiB contiguous
+// per wave and load), lane partials run over the panels in order, then a fixed xor tree across the wave.  No atomics.
+__global__ __launch_bounds__(256) void var_rows_kernel(const double *__restrict__ Bt, int64_t Mp, int nP, int64_t rows,
+                                                       const double *__restrict__ kss, double amp, double *__restrict__ var) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= rows) return;                                       // whole waves leave together
+    const double *row = Bt + i * TGP_PW + 2 * lane;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int p = 0; p < nP; ++p) {
+        const double2 a = *(const double2 *)(row + (int64_t)p * Mp * TGP_PW);
+        const double2 b = *(const double2 *)(row + (int64_t)p * Mp * TGP_PW + 128);
+        acc += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) var[i] = (kss ? kss[i] : amp) - acc;
+}
+
+// rows per chunk: TGP_VAR_CHUNK (rounded up to 256) or the default, at most TGP_VAR_CHUNK_MAX, and at most what keeps the
+// chunk's Bt (Mc x Np) plus the substitution's staging (Mc x 1024, scratch2) within half of the device memory that is free or
+// already held as scratch by this context; never more than m needs
+int var_chunk_rows(tgp_ctx *ctx, const tgp_factor *f, int64_t m, int64_t *Mc) {
+    int64_t want = TGP_VAR_CHUNK_DEFAULT;
+    const char *e = getenv("TGP_VAR_CHUNK");                     // read per call (tests, A/B runs), as TGP_COV_BIG is
+    if (e && atoll(e) > 0) want = (atoll(e) + TGP_PW - 1) / TGP_PW * TGP_PW;
+    if (want > TGP_VAR_CHUNK_MAX) want = TGP_VAR_CHUNK_MAX;
+    size_t fr = 0, tot = 0;
+    TGP_HIP(hipMemGetInfo(&fr, &tot));
+    const double avail = (double)fr + (double)ctx->scratch_bytes + (double)ctx->scratch2_bytes;
+    int64_t cap = (int64_t)(0.5 * avail / ((double)(f->Np + 1024) * sizeof(double))) / TGP_PW * TGP_PW;
+    if (cap < TGP_PW) cap = TGP_PW;
+    const int64_t need = (m + TGP_PW - 1) / TGP_PW * TGP_PW;
+    *Mc = want < cap ? want : cap;
+    if (need < *Mc) *Mc = need;
+    return 0;
+}
+
+// HT of every chunk is written into pl.d_Bt by `fill` (rows r0 .. r0 + rows of the queries, Mp rows of panels, zero padded),
+// the dense route's k(x_i, x_i) into pl.d_kss; then substitution, norms, the chunk's variances to var + r0.
+// Timings: [3] device compute, [9] transfer of the result, each summed over the chunks.
+template <class Fill>
+int var_chunks(tgp_ctx *ctx, tgp_factor *f, CovPlan &pl, int64_t Mc, double amp, bool dense, double *var, Fill fill) {
+    hipStream_t st = ctx->stream;
+    double t_dev = 0.0, t_d2h = 0.0;
+    for (int64_t r0 = 0; r0 < pl.m; r0 += Mc) {
+        const int64_t rows = (pl.m - r0) < Mc ? (pl.m - r0) : Mc;
+        CovPlan cp = pl;
+        cp.Mp = (rows + TGP_PW - 1) / TGP_PW * TGP_PW;          // a short last chunk substitutes only the rows it has
+        cp.nPm = (int)(cp.Mp / TGP_PW);
+        if (r0 > 0) TGP_HIP(hipEventRecord(ctx->ev[0], st));     // (the first chunk's interval starts before the uploads)
+        int rc = fill(cp, r0, rows);
+        if (rc) return rc;
+        rc = cov_substitute(ctx, f, cp, false);
+        if (rc) return rc;
+        var_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(cp.d_Bt, cp.Mp, cp.nP, rows, dense ? cp.d_kss : nullptr, amp, cp.d_v);
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipEventRecord(ctx->ev[1], st));
+        TGP_HIP(hipMemcpyAsync(var + r0, cp.d_v, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipEventRecord(ctx->ev[2], st));
+        TGP_HIP(hipStreamSynchronize(st));
+        float ms = 0.f;
+        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        t_dev += ms;
+        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+        t_d2h += ms;
+    }
+    ctx->timings[3] = t_dev;                    // device compute
+    ctx->timings[9] = t_d2h;                    // (m) result to the caller's buffer
+    return 0;
+}
+}  // namespace
+
+extern "C" int tgp_gp_predict_var(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n,
+                                  const double *Xs, int64_t m, double *var) {
+    TGP_ARG(f && k && X && Xs && var && m > 0 && n == f->n);
+    TGP_ARG(kind_to_ke(k->kind) >= 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int64_t Mc = 0;
+    int rc = var_chunk_rows(ctx, f, m, &Mc);
+    if (rc) return rc;
+    CovPlan pl;
+    rc = cov_plan(ctx, f, m, true, &pl, Mc);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(pl.d_X, X, 2 * n * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(pl.d_Xs, Xs, 2 * m * 8, hipMemcpyHostToDevice, st));
+    // k(x_i, x_i) of the four parametrised kinds is exactly amp (the self kernel's diagonal, tgp_kernel_matrix)
+    return var_chunks(ctx, f, pl, Mc, k->amp, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows) {
+        return launch_cross_panels(ctx, k, cp.d_Xs + 2 * r0, rows, cp.d_X, n, 0, cp.d_Bt, cp.Mp, cp.Np);
+    });
+}
+
+// The same with HT = kernel(X2, Y=X1) (m, n) and kss = kernel.diag(X2) (m) evaluated by the caller (host arrays).
+extern "C" int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const double *HT, const double *kss, int64_t m, double *var) {
+    TGP_ARG(f && HT && kss && var && m > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int64_t Mc = 0;
+    int rc = var_chunk_rows(ctx, f, m, &Mc);
+    if (rc) return rc;
+    CovPlan pl;
+    rc = cov_plan(ctx, f, m, false, &pl, Mc);
+    if (rc) return rc;
+    const int64_t n = f->n;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    return var_chunks(ctx, f, pl, Mc, 0.0, true, var, [&](const CovPlan &cp, int64_t r0, int64_t rows) -> int {
+        TGP_HIP(hipMemsetAsync(cp.d_Bt, 0, (size_t)cp.Mp * cp.Np * 8, st));
+        for (int p = 0; p < cp.nP; ++p) {
+            const int64_t w = (n - (int64_t)p * TGP_PW < TGP_PW) ? n - (int64_t)p * TGP_PW : TGP_PW;
+            if (w <= 0) break;
+            TGP_HIP(hipMemcpy2DAsync(cp.d_Bt + (int64_t)p * cp.Mp * TGP_PW, (size_t)TGP_PW * 8, HT + r0 * n + (int64_t)p * TGP_PW,
+                                     (size_t)n * 8, (size_t)w * 8, (size_t)rows, hipMemcpyHostToDevice, st));
+        }
+        TGP_HIP(hipMemcpyAsync(cp.d_kss, kss + r0, (size_t)rows * 8, hipMemcpyHostToDevice, st));
+        return 0;
+    });
 }
 
 // ---- gradient of the log marginal likelihood (kernel derivative convention of treegp/kernels.py:128-150) ------------

@@ -118,48 +118,60 @@ class GPInterpolation(object):
         return h.digest()
 
     # -- prediction ------------------------------------------------------------------------------
-    def predict(self, X, return_cov=False):
+    def predict(self, X, return_cov=False, return_var=False):
         """Interpolated values (and optionally the posterior covariance) at X (n_samples, 1 or 2).
-        gp_interp.py:143-166: the GP acts on y - mean - mean function; both are added back."""
+        gp_interp.py:143-166: the GP acts on y - mean - mean function; both are added back.
+        Not in the reference: ``return_var=True`` returns (y, var) with var (n_samples,) = the diagonal of what
+        ``return_cov=True`` returns, without forming the covariance (any number of points; not clamped at zero)."""
+        if return_cov and return_var:
+            raise ValueError("at most one of return_cov and return_var may be True")
         residual = self._y - self._mean - self._spatial_average
         with self._scope():
-            y_star, y_cov = self.return_gp_predict(residual, self._X, X, self.kernel, y_err=self._y_err,
-                                                   return_cov=return_cov)
+            y_star, y_unc = self.return_gp_predict(residual, self._X, X, self.kernel, y_err=self._y_err,
+                                                   return_cov=return_cov, return_var=return_var)
         y_star = y_star + (self._mean + self._build_average_meanify(X))
-        return (y_star, y_cov) if return_cov else y_star
+        return (y_star, y_unc) if (return_cov or return_var) else y_star
 
-    def return_gp_predict(self, y, X1, X2, kernel, y_err, return_cov=False):
+    def return_gp_predict(self, y, X1, X2, kernel, y_err, return_cov=False, return_var=False):
         """gp_interp.py:168-194 on the GPU: fused K build + Cholesky + solve (tgp_gp_solve), fused
         cross-kernel mat-vec (tgp_gp_predict) and, for return_cov, Kss - HT K^-1 HT^T from the
-        factor kept on the device (tgp_gp_predict_cov) instead of a second factorisation."""
+        factor kept on the device (tgp_gp_predict_cov) instead of a second factorisation; for return_var
+        its diagonal alone from the same kept factor (tgp_gp_predict_var)."""
+        if return_cov and return_var:
+            raise ValueError("at most one of return_cov and return_var may be True")
         try:
             spec = kernel_to_spec(kernel)
         except NotImplementedError:
             # any other scikit-learn kernel tree (Sum, WhiteKernel, Matern, ...): the kernel object evaluates itself on
             # the host, exactly as in the reference, and the device factorises what it returns (tgp_gp_solve_dense)
-            return self._return_gp_predict_dense(y, X1, X2, kernel, y_err, return_cov)
+            return self._return_gp_predict_dense(y, X1, X2, kernel, y_err, return_cov, return_var)
         # The reference caches only alpha (computed when it is None, whatever the arguments: gp_interp.py:179) and
         # rebuilds K + diag(y_err^2) from its ARGUMENTS for every covariance request (:186-187).  The factor kept on the
         # device therefore carries the fingerprint of what it was built from and is rebuilt when that differs.
-        key = self._factor_fingerprint(spec, X1, y_err) if return_cov else None
+        want_factor = return_cov or return_var
+        key = self._factor_fingerprint(spec, X1, y_err) if want_factor else None
         if self._alpha is None:
-            self._alpha, _, _, factor = ops.gp_solve(spec, X1, y, y_err, keep=return_cov)
+            self._alpha, _, _, factor = ops.gp_solve(spec, X1, y, y_err, keep=want_factor)
             self._set_factor(factor, key)
-        elif return_cov and (self._factor is None or self._factor_key != key):
+        elif want_factor and (self._factor is None or self._factor_key != key):
             factor = ops.gp_solve(spec, X1, y, y_err, keep=True)[3]          # alpha stays the cached one, as in the reference
             self._set_factor(factor, key)
         y_predict = ops.gp_predict(spec, X1, self._alpha, X2)
         if return_cov:
             y_cov = ops.gp_predict_cov(spec, self._factor, X1, X2)
             return y_predict, y_cov
+        if return_var:
+            return y_predict, ops.gp_predict_var(spec, self._factor, X1, X2)
         return y_predict, None
 
-    def _return_gp_predict_dense(self, y, X1, X2, kernel, y_err, return_cov):
+    def _return_gp_predict_dense(self, y, X1, X2, kernel, y_err, return_cov, return_var=False):
         """gp_interp.py:177-192 for a kernel only scikit-learn can evaluate: HT, K and k(X2) come from ``kernel.__call__``
-        on the host; factorisation, solve and the posterior covariance run on the device."""
+        on the host; factorisation, solve and the posterior covariance run on the device.  For return_var the diagonal
+        of k(X2) is ``kernel.diag(X2)`` (WhiteKernel's noise included, as in diag(kernel(X2)))."""
         HT = kernel(X2, Y=X1)
+        want_factor = return_cov or return_var
         key = None
-        if return_cov:
+        if want_factor:
             import hashlib
             h = hashlib.blake2b(digest_size=16)
             h.update(repr(kernel).encode())
@@ -170,14 +182,16 @@ class GPInterpolation(object):
                 h.update(arr.tobytes())
             key = h.digest()
         need_alpha = self._alpha is None
-        if need_alpha or (return_cov and (self._factor is None or self._factor_key != key)):
-            alpha, _, _, factor = ops.gp_solve_dense(kernel(X1), y, y_err, keep=return_cov)
+        if need_alpha or (want_factor and (self._factor is None or self._factor_key != key)):
+            alpha, _, _, factor = ops.gp_solve_dense(kernel(X1), y, y_err, keep=want_factor)
             if need_alpha:
                 self._alpha = alpha
             self._set_factor(factor, key)
         y_predict = np.dot(HT, self._alpha.reshape((len(self._alpha), 1))).T[0]
         if return_cov:
             return y_predict, ops.gp_predict_cov_dense(self._factor, HT, kernel(X2))
+        if return_var:
+            return y_predict, ops.gp_predict_var_dense(self._factor, HT, kernel.diag(X2))
         return y_predict, None
 
     def predict_fields(self, Y, X, y_err=None):

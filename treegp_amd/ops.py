@@ -161,6 +161,20 @@ def gp_predict_cov_dense(factor, HT, Kss, ctx=None):
     return cov
 
 
+def gp_predict_var_dense(factor, HT, kss, ctx=None):
+    """diag(Kss - HT (K + D)^-1 HT^T) for caller-evaluated HT = kernel(X2, Y=X1) (m, n) and kss = kernel.diag(X2) (m),
+    without forming the (m, m) covariance (tgp_gp_predict_var_dense)."""
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    HT, kss = f64(HT), f64(kss)
+    m = HT.shape[0]
+    if HT.shape != (m, factor.n) or kss.shape != (m,):
+        raise ValueError("HT must be (m, n) and kss (m,)")
+    var = np.empty(m)
+    check(ctx, lib.tgp_gp_predict_var_dense(ctx, factor._h, ptr(HT), ptr(kss), m, ptr(var)), "tgp_gp_predict_var_dense")
+    return var
+
+
 class ResidentProblem(object):
     """X, y, y_err of one GP problem kept on the device (``tgp_dev_alloc`` / ``tgp_h2d``) for a series of solves
     that differ only in the kernel -- the likelihood evaluations of a maximum-likelihood fit.  Uploading the three
@@ -250,6 +264,19 @@ def gp_predict_cov(spec, factor, X, Xs, ctx=None):
     rc = lib.tgp_gp_predict_cov(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(Xs2), m, ptr(cov))
     check(ctx, rc, "tgp_gp_predict_cov")
     return cov
+
+
+def gp_predict_var(spec, factor, X, Xs, ctx=None):
+    """Posterior variance diag(k(Xs,Xs) - HT K^-1 HT^T) from a kept factor, for any number of query points: the (m, m)
+    covariance is never formed (tgp_gp_predict_var; the reference's callers take np.diag of gp_interp.py:184-192)."""
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    X2, Xs2 = as_xy(X), as_xy(Xs)
+    m = Xs2.shape[0]
+    var = np.empty(m)
+    rc = lib.tgp_gp_predict_var(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(Xs2), m, ptr(var))
+    check(ctx, rc, "tgp_gp_predict_var")
+    return var
 
 
 def gp_loglik_grad(spec, factor, X, alpha, ctx=None):
