@@ -9,6 +9,7 @@
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
+ *   S3d realisations y = L z             np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66, 95-97
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
  *   S6  binned_statistic_2d              treegp/meanify.py:76-107
@@ -72,8 +73,9 @@ int tgp_device_count(void);
  * [7] trailing-update flops (sum over launches)  [8] K-build bytes written
  * [9] result transfer of tgp_gp_predict_cov / tgp_gp_predict_var ([3] is then its device compute time)
  * [10] triangular sweeps over L inside [2]: 2 = forward + backward, 1 = backward only (the forward substitution
- *      rode along with the factorisation, inside [1]), 0 = none (likelihood only, right-hand side as a matrix row) */
-#define TGP_NTIMINGS 11
+ *      rode along with the factorisation, inside [1]), 0 = none (likelihood only, right-hand side as a matrix row)
+ * [11] device time of the product L Z of tgp_factor_lmul (transfers excluded)                                     */
+#define TGP_NTIMINGS 12
 int tgp_last_timings(tgp_ctx *ctx, double *ms, int n);
 /* when on (default off) the Cholesky brackets every trailing-update launch with events */
 int tgp_set_profiling(tgp_ctx *ctx, int on);
@@ -145,6 +147,13 @@ int tgp_gp_predict_var(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const d
 /* the same with HT = kernel(X2, Y=X1) (m, n) and kss = kernel.diag(X2) (m) evaluated by the caller */
 int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const double *HT, const double *kss,
                              int64_t m, double *var);
+
+/* ---- S3d: realisations -- Yout[v] = L Z[v], L the lower Cholesky factor of K + diag(yerr^2) kept by tgp_gp_solve /
+ * tgp_gp_solve_dense (stands in for np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66,95-97 of
+ * the reference).  Z, Yout: (nrhs, n) row-major host.  L is read once per group of 8 right-hand sides; no atomics: the
+ * result is bit-identical from run to run, and row v of Yout does not depend on the other rows of Z.
+ * Device time in timings[11].                                                                                          */
+int tgp_factor_lmul(tgp_ctx *ctx, tgp_factor *f, const double *Z, int nrhs, double *Yout);
 
 /* ---- S2d: gradient of the log marginal likelihood from a kept factor and its alpha ---------
  * (the reference's optimiser passes no jac, treegp/log_likelihood.py:57 -- this is what a caller who wants one

@@ -14,6 +14,8 @@ from .two_pcf import two_pcf  # noqa: F401  (class shadows the module, as in the
 from .log_likelihood import log_likelihood  # noqa: F401
 from .meanify import meanify  # noqa: F401
 from .utils import comp_eb, comp_eb_treecorr
+from .sampling import gaussian_random_field
 
 __all__ = ["__version__", "__version_info__", "GPInterpolation", "two_pcf", "log_likelihood", "AnisotropicRBF",
-           "VonKarman", "AnisotropicVonKarman", "eval_kernel", "kernel_to_spec", "meanify", "comp_eb", "comp_eb_treecorr"]
+           "VonKarman", "AnisotropicVonKarman", "eval_kernel", "kernel_to_spec", "meanify", "comp_eb", "comp_eb_treecorr",
+           "gaussian_random_field"]

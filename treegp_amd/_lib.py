@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TGP_LIB_PATH") or os.path.join(_HERE, "csrc", "libtgp.so")   # override: A/B builds
 
 TGP_RBF, TGP_ARBF, TGP_VK, TGP_AVK = 0, 1, 2, 3
-NTIMINGS = 11
+NTIMINGS = 12
 
 
 class TgpKernel(C.Structure):
@@ -69,6 +69,7 @@ SIGNATURES = {
     "tgp_gp_solve_dense": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _dp, _dp, C.POINTER(_vp)]),
     "tgp_d_gp_solve_dense": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _dp, _dp, C.POINTER(_vp)]),
     "tgp_factor_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
+    "tgp_factor_lmul": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "tgp_gp_predict_cov_dense": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "tgp_gp_predict_var": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _i64, _vp]),
     "tgp_gp_predict_var_dense": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),

@@ -636,6 +636,34 @@ int tgp_factor_solve(tgp_ctx *ctx, tgp_factor *f, const double *B, int nrhs, dou
     return 0;
 }
 
+// ---- S3d: realisations, Yout[v] = L Z[v] with the factor kept by tgp_gp_solve / tgp_gp_solve_dense ----------------------
+// Z, Yout: (nrhs, n) row-major host (np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66, 95-97 of the
+// reference: y = L z with z standard normal).  Device time in timings[11].
+int tgp_factor_lmul(tgp_ctx *ctx, tgp_factor *f, const double *Z, int nrhs, double *Yout) {
+    TGP_ARG(f && Z && Yout && nrhs > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t n = f->n, Np = f->Np;
+    const size_t zb = (size_t)nrhs * Np * 8;
+    int rc = ensure_io(ctx, 2 * rup(zb) + rup(lmul_partial_bytes(Np, nrhs)));
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_Z = ar.take<double>((size_t)nrhs * Np), *d_Y = ar.take<double>((size_t)nrhs * Np);
+    double *d_part = (double *)(ar.base + ar.off);
+    TGP_HIP(hipMemsetAsync(d_Z, 0, zb, st));
+    TGP_HIP(hipMemcpy2DAsync(d_Z, (size_t)Np * 8, Z, (size_t)n * 8, (size_t)n * 8, (size_t)nrhs, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    rc = launch_factor_lmul(ctx, f->d_A, Np, d_Z, nrhs, d_Y, d_part);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    TGP_HIP(hipMemcpy2DAsync(Yout, (size_t)n * 8, d_Y, (size_t)Np * 8, (size_t)n * 8, (size_t)nrhs, hipMemcpyDeviceToHost, st));
+    TGP_HIP(hipStreamSynchronize(st));
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->timings[11] = ms;
+    return 0;
+}
+
 // the context gives back what it holds between calls: the factor cache of its last solve (17 GB at N = 65 536), inverse slabs,
 // scratch -- for a process about to allocate elsewhere on the same GPU (the multi-GPU engine before its replicated factor)
 int tgp_release_caches(tgp_ctx *ctx) {

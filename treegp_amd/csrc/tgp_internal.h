@@ -266,3 +266,6 @@ int launch_pack_lower(tgp_ctx *ctx, const double *d_K, int64_t n, int64_t Np, co
 // d_B: (nrhs, Np) right-hand sides, solved in place, the factor read once per sweep for groups of up to 8 of them
 int launch_potrs_multi(tgp_ctx *ctx, const double *d_A, const double *d_W, int64_t Np, double *d_B, int nrhs, double **slab_cache,
                        int *slab_S = nullptr);
+// lmul.hip: d_Y (nrhs, Np) = L d_Z with the packed lower factor; d_partial holds lmul_partial_bytes(Np, nrhs)
+size_t lmul_partial_bytes(int64_t Np, int nrhs);
+int launch_factor_lmul(tgp_ctx *ctx, const double *d_A, int64_t Np, const double *d_Z, int nrhs, double *d_Y, double *d_partial);

@@ -194,6 +194,24 @@ class GPInterpolation(object):
             return y_predict, ops.gp_predict_var_dense(self._factor, HT, kernel.diag(X2))
         return y_predict, None
 
+    def sample_y(self, X, n_samples=1, random_state=0, nugget=1e-10):
+        """Realisations of the posterior at X (n_points, 1 or 2): (n_points, n_samples), scikit-learn's ``sample_y``
+        layout (not in the reference).  y_star + L* z with y_star, cov = ``predict(X, return_cov=True)`` (mean, meanify and
+        the kept factor included), L* the Cholesky factor of cov + jitter I, jitter = nugget * max k(x, x), and z the v-th
+        row of ``np.random.default_rng(random_state).standard_normal((n_samples, n_points))`` for realisation v.
+        The posterior covariance comes through ``predict`` under this object's backend; its factorisation and the
+        product run on one GPU (no multi-GPU sampling).  The cached solution is left as ``predict`` leaves it.
+        Raises numpy.linalg.LinAlgError when cov + jitter I is not positive definite (raise ``nugget``), ValueError for
+        n_samples < 1, nugget < 0 or X that does not match the kernel."""
+        from . import sampling
+        sampling.check_sampling_args(n_samples, nugget)
+        X = sampling.as_coords(self.kernel, X)
+        y_star, cov = self.predict(X, return_cov=True)
+        C = np.array(cov, dtype=np.float64)
+        C[np.diag_indices(len(C))] += nugget * sampling.prior_diag_max(self.kernel, X)
+        Y = sampling.lmul_dense(C, sampling.normals(n_samples, len(X), random_state), nugget)
+        return y_star[:, None] + Y.T
+
     def predict_fields(self, Y, X, y_err=None):
         """Several fields measured at the SAME positions with the same kernel and errors (one GP per PSF parameter, the Piff
         pattern of treegp/README.rst:28; with the reference each field is its own GPInterpolation, i.e. its own K build,

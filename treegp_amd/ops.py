@@ -148,6 +148,20 @@ def factor_solve(factor, B, ctx=None):
     return out
 
 
+def factor_lmul(factor, Z, ctx=None):
+    """L applied to every row of Z (nrhs, n) with a kept factor, L the lower Cholesky factor of K + D (tgp_factor_lmul):
+    rows of standard normals become realisations of N(0, K + D).  The factor is read once per group of 8 rows; row v of
+    the result does not depend on the other rows of Z."""
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    Z = np.atleast_2d(f64(Z))
+    if Z.ndim != 2 or Z.shape[1] != factor.n:
+        raise ValueError("Z must be (nrhs, %d)" % factor.n)
+    out = np.empty_like(Z)
+    check(ctx, lib.tgp_factor_lmul(ctx, factor._h, ptr(Z), Z.shape[0], ptr(out)), "tgp_factor_lmul")
+    return out
+
+
 def gp_predict_cov_dense(factor, HT, Kss, ctx=None):
     """Kss - HT (K + D)^-1 HT^T for caller-evaluated HT = kernel(X2, Y=X1) (m, n) and Kss = kernel(X2) (m, m)."""
     ctx = ctx or factor._ctx
