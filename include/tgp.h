@@ -6,6 +6,7 @@
  *
  *   S1  kernel.__call__(X[,Y])           treegp/kernels.py:114-126, 249-276, 355-381
  *   S2  cholesky + cho_solve (+ logdet)  treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33
+ *   S2e many small S2 at once           treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33, 43-62, README.rst:28
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
@@ -124,6 +125,23 @@ int tgp_gp_solve_dense(tgp_ctx *ctx, const double *K, int64_t n, const double *y
  * its own cholesky + cho_solve, gp_interp.py:180-182).  B and Xout: (nrhs, n) row-major;
  * Xout[v] = (K + diag(yerr^2))^-1 B[v].  The factor is read once per sweep for up to 4 fields.  */
 int tgp_factor_solve(tgp_ctx *ctx, tgp_factor *f, const double *B, int nrhs, double *Xout);
+
+/* ---- S2e: S2 for nb independent small problems in ONE launch sequence ------------------------------------------
+ * The reference's regime is many small GPs: one per PSF parameter, exposure or chip (README.rst:28), each its own
+ * cholesky + cho_solve (treegp/gp_interp.py:180-182), and 37-82 independent likelihood evaluations per maximum-likelihood
+ * fit (treegp/log_likelihood.py:29-33, 43-62).  Problem b has its own kernel ks[b] (kinds may differ), order ns[b]
+ * (1 <= ns[b] <= nmax <= 4096; above that one solve alone fills the chip: tgp_gp_solve), coordinates X (nb, nmax, 2),
+ * values y (nb, nmax) and errors yerr (nb, nmax, or NULL); rows >= ns[b] are ignored.  Outputs: alpha (nb, nmax) or NULL,
+ * entries >= ns[b] set to 0; logdet (nb); ydota (nb) = |L^-1 y|^2 or NULL; info (nb): 0, or > 0 = LAPACK-style order of
+ * the failing minor of problem b, whose outputs are then meaningless -- the other problems' are unaffected, bit for bit.
+ * A problem's bits depend neither on its companions, nor on its place in the batch, nor on the chunking: the batch runs
+ * in chunks of as many problems as 90 % of the free device memory holds (TGP_BATCH_CHUNK problems per chunk overrides),
+ * in the context's workspace (given back by tgp_release_caches).
+ * Returns 0 when every problem was attempted; -1 for nb < 1, nmax > 4096, ns[b] out of range or an unknown kind; -2 for
+ * HIP errors.  Timings [0] K build, [1] Cholesky, [2] sweeps and logdet, summed over the chunks; [10] sweeps (2, or 1
+ * without alpha); every other slot 0.                                                                                  */
+int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                       const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info);
 
 /* ---- S3: ys[j] = sum_i amp k(Xs_j, X_i) alpha_i, HT never materialised -------------------*/
 int tgp_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n,

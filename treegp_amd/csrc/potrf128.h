@@ -876,6 +876,9 @@ __device__ __forceinline__ void potrf128_body(double *T, double *A, int lda, dou
 // stays within 256 by rematerialising addresses, without a spill.
 constexpr unsigned POTRF_LDS_BYTES = POTRF_LDS_DOUBLES * sizeof(double);
 extern __shared__ __attribute__((aligned(16))) double potrf_lds_image[];
+// TGP_POTRF_BODY_ONLY: a translation unit that wraps the body in kernels of its own (batch.hip) leaves these two out -- a
+// __global__ function defined in two translation units is defined twice at link time
+#ifndef TGP_POTRF_BODY_ONLY
 template <bool DIAG16>
 __global__ __launch_bounds__(256, 2) void potrf128_kernel(double *A, int lda, double *W, int *info, int base) {
     TGP_CHAIN_PRIO();
@@ -887,4 +890,5 @@ __global__ __launch_bounds__(256) void potrf128_solo_kernel(double *A, int lda, 
     TGP_CHAIN_PRIO();
     potrf128_body<true>(potrf_lds_image, A, lda, W, info, base);
 }
+#endif
 }  // namespace potrf_v2

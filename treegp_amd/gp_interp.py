@@ -307,3 +307,40 @@ class GPInterpolation(object):
 
     def plot_fitted_kernel(self):
         raise NotImplementedError("plotting (treegp/gp_interp.py:293-377) is outside the GPU hot path")
+
+
+def predict_many(gps, Xs):
+    """``[gp.predict(X) for gp, X in zip(gps, Xs)]`` with the solves of many small GPs in one batched factorisation (the
+    reference's regime: one GP per PSF parameter, exposure or chip, README.rst:28).  ``gps``: initialised GPInterpolation
+    objects; ``Xs``: their query points.  The objects whose kernel ``kernel_to_spec`` describes, that are not on the
+    multi-GPU route, hold at most 4096 points and have no cached solution get their alpha from one batched solve
+    (ops.gp_solve_batch); it is cached in ``gp._alpha`` as ``predict`` caches it, so that a later ``gp.predict`` reuses
+    it.  Every object then predicts through its own ``predict``: the others solve there as usual.  A failed
+    factorisation raises numpy.linalg.LinAlgError naming the object's index (nothing is cached then)."""
+    gps, Xs = list(gps), list(Xs)
+    if len(gps) != len(Xs):
+        raise ValueError("predict_many: %d GPs but %d arrays of query points" % (len(gps), len(Xs)))
+    picked, specs = [], []
+    for i, gp in enumerate(gps):
+        if gp._alpha is not None or gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX:
+            continue
+        try:
+            spec = kernel_to_spec(gp.kernel)
+        except NotImplementedError:
+            continue
+        with gp._scope():
+            if ops._dist_engine(len(gp._X), None) is not None:
+                continue
+        picked.append(i)
+        specs.append(spec)
+    if picked:
+        alphas, _, _, info = ops.gp_solve_batch(specs, [gps[i]._X for i in picked], [gps[i]._residual() for i in picked],
+                                                [gps[i]._y_err for i in picked])
+        for j, i in enumerate(picked):
+            if info[j] > 0:
+                raise np.linalg.LinAlgError("predict_many: GP %d: %d-th leading minor of the array is not positive definite"
+                                            % (i, info[j]))
+        for j, i in enumerate(picked):
+            gps[i]._alpha = alphas[j]
+            gps[i]._set_factor(None, None)        # what predict's own solve leaves: no kept factor
+    return [gp.predict(X) for gp, X in zip(gps, Xs)]

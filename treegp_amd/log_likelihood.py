@@ -25,6 +25,7 @@ from .kernels import kernel_to_spec, spec_jacobian
 
 _FD_STEP = 1e-8                  # scipy.optimize.minimize(method="L-BFGS-B") default `eps` (absolute forward step)
 _PARALLEL_MAX_N = 16384          # beyond this one solve fills the GPU by itself
+_BATCH_CALL = 256                # log_likelihood_many: kernels per batched call (the library chunks further by device memory)
 _pool_lock = threading.Lock()
 _ctx_pool = []                   # extra contexts (one stream each) for concurrent evaluations, created on demand
 
@@ -95,6 +96,52 @@ class log_likelihood(object):
         if not np.isfinite(ll):
             ll = -np.inf
         return ll
+
+    def log_likelihood_many(self, kernels):
+        """One log L per kernel, each with exactly ``log_likelihood(kernel)``'s semantics (-inf for a matrix that is not
+        positive definite and for the failures that method turns into -inf).  The kernels ``kernel_to_spec`` describes go
+        through batched solves (ops.gp_solve_batch: one launch sequence for up to _BATCH_CALL of them); other kernel trees,
+        n > 4096 and the multi-GPU route take ``log_likelihood`` one kernel after the other."""
+        kernels = list(kernels)
+        out = np.full(len(kernels), -np.inf)
+        batched = []
+        for i, kernel in enumerate(kernels):
+            spec = None
+            if not self.distributed and self.ndata <= ops.BATCH_NMAX:
+                try:
+                    spec = kernel_to_spec(kernel)
+                except NotImplementedError:
+                    spec = None
+            if spec is None:
+                out[i] = self.log_likelihood(kernel)
+            else:
+                batched.append((i, spec))
+        const = (0.5 * self.ndata) * np.log(2.0 * np.pi)
+        for c0 in range(0, len(batched), _BATCH_CALL):
+            part = batched[c0:c0 + _BATCH_CALL]
+            m = len(part)
+            try:
+                _, log_det, chi2, info = ops.gp_solve_batch([s for _, s in part], [self.X] * m, [self.y] * m,
+                                                            None if self.y_err is None else [self.y_err] * m,
+                                                            want_alpha=False)
+            except (ValueError, TgpError) as ex:
+                # a device error of the batch is judged as one of a single evaluation (_rejects_theta): an argument error, or
+                # any error under TGP_ML_STRICT=1, raises; a run-time one (rc -2: e.g. the batch's memory) warns, and then
+                # every kernel meets what log_likelihood would give it by itself
+                if isinstance(ex, TgpError):
+                    if os.environ.get("TGP_ML_STRICT") == "1" or getattr(ex, "rc", -1) != -2:
+                        raise
+                    import warnings
+                    warnings.warn("batched likelihood evaluation failed on the device, its %d kernels are evaluated one by "
+                                  "one (set TGP_ML_STRICT=1 to raise): %s" % (m, ex), RuntimeWarning, stacklevel=2)
+                for i, _ in part:
+                    out[i] = self.log_likelihood(kernels[i])
+                continue
+            with np.errstate(invalid="ignore", over="ignore"):
+                ll = -0.5 * chi2 - const - 0.5 * log_det
+            for j, (i, _) in enumerate(part):
+                out[i] = ll[j] if info[j] == 0 and np.isfinite(ll[j]) else -np.inf
+        return out
 
     def log_likelihood_gradient(self, kernel, ctx=None, resident=None):
         """(log L, d log L / d theta): 1/2 tr((alpha alpha^T - K^-1) dK/dtheta_k) with the kernel derivative of

@@ -113,6 +113,72 @@ def gp_solve(spec, X, y, y_err=None, keep=False, want_alpha=True, ctx=None):
     return alpha, logdet.value, ydota.value, (Factor(ctx, h, n) if keep else None)
 
 
+BATCH_NMAX = 4096      # tgp_gp_solve_batch: largest order of a problem (above it one solve alone fills the chip)
+
+
+def pad_batch(Xs, ys, y_errs=None):
+    """Lists of per-problem arrays -> (ns, nmax, X (nb, nmax, 2), y (nb, nmax), yerr (nb, nmax) or None), zero beyond n_b.
+    1-D coordinates get a zero second column.  Raises ValueError on any shape mismatch."""
+    Xs, ys = list(Xs), list(ys)
+    nb = len(Xs)
+    if nb < 1:
+        raise ValueError("gp_solve_batch needs at least one problem")
+    if len(ys) != nb:
+        raise ValueError("gp_solve_batch: %d coordinate arrays but %d value arrays" % (nb, len(ys)))
+    if y_errs is not None:
+        y_errs = list(y_errs)
+        if len(y_errs) != nb:
+            raise ValueError("gp_solve_batch: %d coordinate arrays but %d error arrays" % (nb, len(y_errs)))
+    X2s = [as_xy(X) for X in Xs]
+    ns = np.array([X.shape[0] for X in X2s], dtype=np.int64)
+    if np.any(ns < 1):
+        raise ValueError("gp_solve_batch: every problem needs at least one point")
+    nmax = int(ns.max())
+    Xb = np.zeros((nb, nmax, 2))
+    yb = np.zeros((nb, nmax))
+    eb = None if y_errs is None else np.zeros((nb, nmax))
+    for b in range(nb):
+        n = int(ns[b])
+        yv = np.asarray(ys[b], dtype=np.float64).reshape(-1) if np.ndim(ys[b]) <= 1 else None
+        if yv is None or yv.shape[0] != n:
+            raise ValueError("gp_solve_batch: problem %d has %d points but y of shape %r" % (b, n, np.shape(ys[b])))
+        Xb[b, :n] = X2s[b]
+        yb[b, :n] = yv
+        if eb is not None:
+            ev = np.asarray(y_errs[b], dtype=np.float64)
+            if ev.ndim != 1 or ev.shape[0] != n:
+                raise ValueError("gp_solve_batch: problem %d has %d points but y_err of shape %r" % (b, n, ev.shape))
+            eb[b, :n] = ev
+    return ns, nmax, Xb, yb, eb
+
+
+def gp_solve_batch(specs, Xs, ys, y_errs=None, want_alpha=True, ctx=None):
+    """gp_solve for many independent small problems in one launch sequence (tgp_gp_solve_batch): problem b has kernel
+    specs[b], coordinates Xs[b] (n_b, 1 or 2), values ys[b] (n_b,) and errors y_errs[b] (or none at all), n_b <= 4096.
+    Returns (alphas: list of (n_b,) arrays or None, logdets (nb,), chi2 = y.alpha (nb,), info (nb,) int): info[b] > 0 is
+    the order of the failing leading minor of problem b, whose other outputs are then meaningless.  Each problem's result
+    does not depend on the others in the call."""
+    specs = list(specs)
+    ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("gp_solve_batch: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("gp_solve_batch: problems of order up to %d, got %d (use gp_solve)" % (BATCH_NMAX, nmax))
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    alpha = np.empty((nb, nmax)) if want_alpha else None
+    logdet = np.empty(nb)
+    chi2 = np.empty(nb)
+    info = np.zeros(nb, dtype=np.int32)
+    rc = lib.tgp_gp_solve_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(alpha),
+                                ptr(logdet), ptr(chi2), ptr(info))
+    check(ctx, rc, "tgp_gp_solve_batch")
+    alphas = [alpha[b, :int(ns[b])].copy() for b in range(nb)] if want_alpha else None
+    return alphas, logdet, chi2, info.astype(np.int64)
+
+
 def gp_solve_dense(K, y, y_err=None, keep=False, want_alpha=True, ctx=None):
     """gp_solve for a kernel matrix evaluated by the caller (any scikit-learn kernel tree): K (n, n), lower triangle
     read; y_err^2 is added to the diagonal on the device (tgp_gp_solve_dense)."""
