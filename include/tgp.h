@@ -11,6 +11,7 @@
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
  *   S3d realisations y = L z             np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66, 95-97
+ *   S3e diag(K^-1) of a kept factor      not in the reference: leave-one-out residuals and variances (R&W 5.4.2)
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
  *   S6  binned_statistic_2d              treegp/meanify.py:76-107
@@ -172,6 +173,14 @@ int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const double *HT, cons
  * result is bit-identical from run to run, and row v of Yout does not depend on the other rows of Z.
  * Device time in timings[11].                                                                                          */
 int tgp_factor_lmul(tgp_ctx *ctx, tgp_factor *f, const double *Z, int nrhs, double *Yout);
+
+/* ---- S3e: diag(K^-1) -- the leave-one-out quantities of a GP (Rasmussen & Williams 5.4.2, eqs. 5.10-5.12) need
+ * alpha = K^-1 r and this diagonal alone.  d (n) = diag((K + diag(yerr^2))^-1) from a factor kept by tgp_gp_solve /
+ * tgp_gp_solve_dense / tgp_factor_borrow: d_i = |L^-1 e_i|^2, identity rows substituted on the device in chunks of
+ * TGP_INVDIAG_CHUNK rows (rounded up to the substitution's step, 1024 or 256), each from its own first column on
+ * (~n^3 / 3 flops in all, no n x n buffer).  The result does not depend on the chunk.
+ * Timings: [3] device compute, [9] transfer, each summed over the chunks.                                              */
+int tgp_factor_inv_diag(tgp_ctx *ctx, tgp_factor *f, double *d);
 
 /* ---- S2d: gradient of the log marginal likelihood from a kept factor and its alpha ---------
  * (the reference's optimiser passes no jac, treegp/log_likelihood.py:57 -- this is what a caller who wants one

@@ -53,25 +53,26 @@ __global__ __launch_bounds__(256, 2) void cov_trsm_kernel(double *Bk, const doub
 }
 
 // Bt[:, c] -= Bt[:, kb] L[c, kb]^T for c = kb + 1 + blockIdx.y
-__global__ __launch_bounds__(256, 2) void cov_update_kernel(double *Bt, int64_t Mp, const double *A, int64_t Np, int kb) {
+// Bt holds the panels from pb on (panel p at Bt + (p - pb) * Mp * 256; pb = 0 but for tgp_factor_inv_diag's chunks)
+__global__ __launch_bounds__(256, 2) void cov_update_kernel(double *Bt, int64_t Mp, const double *A, int64_t Np, int kb, int64_t pb) {
     const int64_t ti = blockIdx.x;
     const int64_t c = kb + 1 + blockIdx.y;
     const int64_t p = kb >> 1;
-    const double *a = Bt + p * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (kb & 1) * TGP_TB;
+    const double *a = Bt + (p - pb) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (kb & 1) * TGP_TB;
     const double *b = A + panel_off(p, Np) + (c * TGP_TB - p * TGP_PW) * TGP_PW + (kb & 1) * TGP_TB;
-    double *cc = Bt + (c >> 1) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
+    double *cc = Bt + ((c >> 1) - pb) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
     gemm_tile_dtv<4, TGP_TB, 1>(a, b, cc, nullptr, nullptr);
 }
 
 // ---- the substitution in steps of S = 1024 (512) columns, with the factor's inverse slabs (trsv_big.hip) -------------------------
 //   T  = Bt[:, K] V_K^T            (V_K = inverse of the S x S diagonal block: k <= j, 256-deep segments; out of place)
 //   Bt[:, c] -= Bt[:, K] L[c, K]^T  for the tile columns c right of super-block K, ONE pass of depth 1024 on the DTV tile
-// instead of eight dependent pairs of depth-128 launches per super-block.
+// instead of eight dependent pairs of depth-128 launches per super-block.  Bt starts at panel pb, as in cov_update_kernel.
 __global__ __launch_bounds__(256) void cov_diag_big_kernel(const double *__restrict__ Bt, int64_t Mp, const double *__restrict__ V,
-                                                           int64_t Np, int64_t r0, int ncolt, double *__restrict__ T) {
+                                                           int64_t Np, int64_t r0, int ncolt, double *__restrict__ T, int64_t pb) {
     const int ti = blockIdx.x / ncolt, tj = blockIdx.x % ncolt;          // 128-row tile of the queries, 128-column tile of the block
     const int64_t p0 = r0 >> 8;
-    const double *a = Bt + p0 * Mp * TGP_PW + (int64_t)ti * TGP_TB * TGP_PW;
+    const double *a = Bt + (p0 - pb) * Mp * TGP_PW + (int64_t)ti * TGP_TB * TGP_PW;
     const double *b = V + (r0 + (int64_t)tj * TGP_TB) * TGP_PW;          // slab panel 0, rows r0 + 128 tj ..
     double *c = T + (int64_t)(tj >> 1) * Mp * TGP_PW + (int64_t)ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
     const int nseg = (tj >> 1) + 1;                                      // V_K is lower triangular: columns k <= j
@@ -79,17 +80,18 @@ __global__ __launch_bounds__(256) void cov_diag_big_kernel(const double *__restr
 }
 
 template <int NS>                                                          // NS = S / 256 panels per super-block
-__global__ __launch_bounds__(256, 2) void cov_update_big_kernel(double *Bt, int64_t Mp, const double *A, int64_t Np, int64_t r0) {
+__global__ __launch_bounds__(256, 2) void cov_update_big_kernel(double *Bt, int64_t Mp, const double *A, int64_t Np, int64_t r0,
+                                                                int64_t pb) {
     const int64_t ti = blockIdx.x;
     const int64_t p0 = r0 >> 8;
     const int64_t c = (r0 >> 7) + 2 * NS + blockIdx.y;                   // global 128-tile column right of the super-block
     SegPtrs<NS> sp;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
-        sp.a[s] = Bt + (p0 + s) * Mp * TGP_PW + ti * TGP_TB * TGP_PW;
+        sp.a[s] = Bt + (p0 + s - pb) * Mp * TGP_PW + ti * TGP_TB * TGP_PW;
         sp.b[s] = A + panel_off(p0 + s, Np) + (c * TGP_TB - (p0 + s) * TGP_PW) * TGP_PW;
     }
-    double *cc = Bt + (c >> 1) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
+    double *cc = Bt + ((c >> 1) - pb) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
     gemm_tile_dtv_segs<4, TGP_PW, NS>(sp, cc);
 }
 
@@ -106,10 +108,13 @@ namespace {
 // geometry + scratch shared by the entry points.  Covariance (var_rows == 0): Bt is Mp x Np, the result d_C Mp x Mp.
 // Variance (var_rows > 0, seam S3c): Bt holds one chunk of Mp = var_rows query rows and there is no d_C; d_v and d_kss are Mp
 // doubles each (the chunk's variances, the caller's k(x_i, x_i) of the dense route).  d_Xs holds all m query points either way.
+// c0: first column of Bt that is stored (a multiple of the substitution's step): d_Bt holds the panels from c0 / 256 on and the
+// substitution starts there.  0 but for the chunks of tgp_factor_inv_diag, whose columns left of c0 are known to be zero.
 struct CovPlan {
     int64_t n, m, Np, Mp;
     int nP, nPm;
     double *d_X, *d_Xs, *d_Bt, *d_C, *d_v, *d_kss;
+    int64_t c0 = 0;
 };
 int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan *pl, int64_t var_rows = 0) {
     pl->n = f->n; pl->m = m; pl->Np = f->Np;
@@ -133,42 +138,59 @@ int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan 
     pl->d_kss = var_rows ? take((size_t)pl->Mp * 8) : nullptr;
     return 0;
 }
-// Bt <- Bt L^-T by block substitution.  `tri`: Bt starts as the identity (m == n), so at the step that eliminates columns
-// [r0, r0 + rows) only the row tiles above r0 + rows hold anything: the launches cover those tiles only (a third of the work).
+// The substitution's step and the factor's inverse slabs: S = 1024 (512) with slabs (built on first use, factor_slabs), S = 0 for
+// the 128-block substitution (below the big-step size, or TGP_COV_BIG=0).
+int cov_step(tgp_ctx *ctx, tgp_factor *f, int *S, const double **slabs) {
+    const bool no_big = getenv("TGP_COV_BIG") && atoi(getenv("TGP_COV_BIG")) == 0;     // A/B: the 128-block substitution
+    *S = 0;
+    *slabs = nullptr;
+    if (!no_big) {
+        int rc = factor_slabs(ctx, f, 1024, S, slabs);
+        if (rc) return rc;
+    }
+    if (!((*S == 1024 || *S == 512) && *slabs)) *S = 0;
+    return 0;
+}
+// Bt <- Bt L^-T by block substitution.  `tri`: row i of Bt starts as e_i (identity rows from c0 on: row tile t of Bt is global
+// row tile c0 / 128 + t), so at the step that eliminates columns [r0, r0 + rows) only the row tiles above r0 + rows hold anything:
+// the launches cover those tiles only (a third of the work).
 int cov_substitute(tgp_ctx *ctx, tgp_factor *f, const CovPlan &pl, bool tri) {
     hipStream_t st = ctx->stream;
     const int nb = 2 * pl.nP;
     const unsigned mt = (unsigned)(pl.Mp / TGP_TB);
-    const bool no_big = getenv("TGP_COV_BIG") && atoi(getenv("TGP_COV_BIG")) == 0;     // A/B: the 128-block substitution
+    const int64_t pb = pl.c0 >> 8;
     int S = 0;
     const double *slabs = nullptr;
-    if (!no_big) {
-        int rc = factor_slabs(ctx, f, 1024, &S, &slabs);
-        if (rc) return rc;
-    }
-    if ((S == 1024 || S == 512) && slabs) {
-        int rc = tgp_ensure_scratch2(ctx, (size_t)pl.Mp * S * sizeof(double));
+    int rc = cov_step(ctx, f, &S, &slabs);
+    if (rc) return rc;
+    TGP_ARG(pl.c0 % (S ? S : TGP_PW) == 0);
+    auto live = [&](int64_t end) {                          // row tiles that are not all zero before the step that ends at `end`
+        const int64_t t = (end - pl.c0) / TGP_TB;
+        return (unsigned)(t < (int64_t)mt ? t : (int64_t)mt);
+    };
+    if (S) {
+        rc = tgp_ensure_scratch2(ctx, (size_t)pl.Mp * S * sizeof(double));
         if (rc) return rc;
         double *T = (double *)ctx->scratch2;
-        for (int64_t r0 = 0; r0 < pl.Np; r0 += S) {
+        for (int64_t r0 = pl.c0; r0 < pl.Np; r0 += S) {
             const int64_t rows = (pl.Np - r0) < S ? (pl.Np - r0) : S;
             const int ncolt = (int)(rows / TGP_TB);
-            const unsigned mte = tri ? (unsigned)((r0 + rows) / TGP_TB) : mt;          // row tiles that are not all zero yet
-            cov_diag_big_kernel<<<mte * (unsigned)ncolt, 256, 0, st>>>(pl.d_Bt, pl.Mp, slabs, pl.Np, r0, ncolt, T);
+            const unsigned mte = tri ? live(r0 + rows) : mt;
+            cov_diag_big_kernel<<<mte * (unsigned)ncolt, 256, 0, st>>>(pl.d_Bt, pl.Mp, slabs, pl.Np, r0, ncolt, T, pb);
             for (int64_t q = 0; q < rows / TGP_PW; ++q)
-                TGP_HIP(hipMemcpyAsync(pl.d_Bt + ((r0 >> 8) + q) * pl.Mp * TGP_PW, T + q * pl.Mp * TGP_PW,
+                TGP_HIP(hipMemcpyAsync(pl.d_Bt + ((r0 >> 8) + q - pb) * pl.Mp * TGP_PW, T + q * pl.Mp * TGP_PW,
                                        (size_t)mte * TGP_TB * TGP_PW * sizeof(double), hipMemcpyDeviceToDevice, st));
             const int64_t right = (pl.Np - (r0 + rows)) / TGP_TB;
-            if (right > 0 && S == 1024) cov_update_big_kernel<4><<<dim3(mte, (unsigned)right), 256, 0, st>>>(pl.d_Bt, pl.Mp, f->d_A, pl.Np, r0);
-            if (right > 0 && S == 512) cov_update_big_kernel<2><<<dim3(mte, (unsigned)right), 256, 0, st>>>(pl.d_Bt, pl.Mp, f->d_A, pl.Np, r0);
+            if (right > 0 && S == 1024) cov_update_big_kernel<4><<<dim3(mte, (unsigned)right), 256, 0, st>>>(pl.d_Bt, pl.Mp, f->d_A, pl.Np, r0, pb);
+            if (right > 0 && S == 512) cov_update_big_kernel<2><<<dim3(mte, (unsigned)right), 256, 0, st>>>(pl.d_Bt, pl.Mp, f->d_A, pl.Np, r0, pb);
         }
     } else {
-        for (int kb = 0; kb < nb; ++kb) {
-            double *Bk = pl.d_Bt + (int64_t)(kb >> 1) * pl.Mp * TGP_PW + (kb & 1) * TGP_TB;
-            const unsigned mte = tri ? (unsigned)(kb + 1) : mt;
+        for (int kb = (int)(pl.c0 / TGP_TB); kb < nb; ++kb) {
+            double *Bk = pl.d_Bt + ((int64_t)(kb >> 1) - pb) * pl.Mp * TGP_PW + (kb & 1) * TGP_TB;
+            const unsigned mte = tri ? live((int64_t)(kb + 1) * TGP_TB) : mt;
             cov_trsm_kernel<<<mte, 256, 0, st>>>(Bk, f->d_W + (int64_t)kb * TGP_TB * TGP_TB);
             const int nc = nb - kb - 1;
-            if (nc > 0) cov_update_kernel<<<dim3(mte, (unsigned)nc), 256, 0, st>>>(pl.d_Bt, pl.Mp, f->d_A, pl.Np, kb);
+            if (nc > 0) cov_update_kernel<<<dim3(mte, (unsigned)nc), 256, 0, st>>>(pl.d_Bt, pl.Mp, f->d_A, pl.Np, kb, pb);
         }
     }
     TGP_HIP(hipGetLastError());
@@ -375,6 +397,98 @@ extern "C" int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const doubl
         TGP_HIP(hipMemcpyAsync(cp.d_kss, kss + r0, (size_t)rows * 8, hipMemcpyHostToDevice, st));
         return 0;
     });
+}
+
+// ---- diag(K^-1) from a kept factor (seam S3e): d_i = |L^-1 e_i|^2, row i of Bt = E L^-T -------------------------------------
+// The leave-one-out quantities of a GP (Rasmussen & Williams 5.4.2) need alpha = K^-1 r and this diagonal.  Identity rows go
+// through the substitution above in chunks [r0, r0 + R), r0 and R multiples of its step (1024 with the inverse slabs, 256 on
+// the 128-block path; the chunks lie on the factor's own super-block grid).  Row i of Bt is zero left of column i, so a chunk
+// stores and updates only the panels from r0 on (R x (Np - r0) doubles), its substitution starts at the super-block r0 and, as
+// for the gradient's L^-T, launches only the row tiles that are not all zero yet (`tri`).  Work sum_chunks R (N - r0)^2 at most,
+// ~N^3 / 3 flops with the row-tile pruning.  The squared row norms are var_rows_kernel's (one wave per row, fixed order, no
+// atomics): rows do not depend on the rows around them, and the zeros a larger chunk carries left of r0 add exact zeros, so the
+// result does not depend on the chunk size.
+#ifndef TGP_INVDIAG_CHUNK_DEFAULT
+#define TGP_INVDIAG_CHUNK_DEFAULT 16384   // identity rows per chunk (LAB_NOTES.md: 4096 - 16 384 measured)
+#endif
+namespace {
+// rows [c0, c0 + Mp) of the identity into a chunk's panels (from panel c0 / 256 on, zeroed before)
+__global__ __launch_bounds__(256) void ident_chunk_kernel(double *Bt, int64_t Mp, int64_t c0) {
+    const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (li >= Mp) return;
+    const int64_t i = c0 + li;
+    Bt[((i >> 8) - (c0 >> 8)) * Mp * TGP_PW + li * TGP_PW + (i & 255)] = 1.0;
+}
+
+// rows per chunk: TGP_INVDIAG_CHUNK (rounded up to the step) or the default, at most the largest multiple of the step that the
+// row grids accept, at most what keeps the chunk (R x Np) and the substitution's staging (R x 1024) within half of the device
+// memory that is free or already held as scratch by this context; never more than n needs
+int inv_diag_chunk_rows(tgp_ctx *ctx, const tgp_factor *f, int64_t step, int64_t *R) {
+    int64_t want = TGP_INVDIAG_CHUNK_DEFAULT;
+    const char *e = getenv("TGP_INVDIAG_CHUNK");                 // read per call (tests, A/B runs)
+    if (e && atoll(e) > 0) want = atoll(e);
+    want = (want + step - 1) / step * step;
+    const int64_t most = TGP_VAR_CHUNK_MAX / step * step;
+    if (want > most) want = most;
+    size_t fr = 0, tot = 0;
+    TGP_HIP(hipMemGetInfo(&fr, &tot));
+    const double avail = (double)fr + (double)ctx->scratch_bytes + (double)ctx->scratch2_bytes;
+    int64_t cap = (int64_t)(0.5 * avail / ((double)(f->Np + 1024) * sizeof(double))) / step * step;
+    if (cap < step) cap = step;
+    const int64_t need = (f->n + step - 1) / step * step;
+    *R = want < cap ? want : cap;
+    if (need < *R) *R = need;
+    return 0;
+}
+}  // namespace
+
+extern "C" int tgp_factor_inv_diag(tgp_ctx *ctx, tgp_factor *f, double *d) {
+    TGP_ARG(f && d && f->n > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t n = f->n;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));                   // (the first chunk's interval includes building the slabs)
+    int S = 0;
+    const double *slabs = nullptr;
+    int rc = cov_step(ctx, f, &S, &slabs);
+    if (rc) return rc;
+    const int64_t step = S ? S : TGP_PW;
+    int64_t R = 0;
+    rc = inv_diag_chunk_rows(ctx, f, step, &R);
+    if (rc) return rc;
+    CovPlan pl;
+    rc = cov_plan(ctx, f, n, false, &pl, R < f->Np ? R : f->Np);   // d_Bt: the first chunk, at most Np x Np
+    if (rc) return rc;
+    double t_dev = 0.0, t_d2h = 0.0;
+    for (int64_t r0 = 0; r0 < n; r0 += R) {
+        const int64_t rows = (n - r0) < R ? (n - r0) : R;
+        CovPlan cp = pl;
+        cp.Mp = (rows + TGP_PW - 1) / TGP_PW * TGP_PW;          // r0 + Mp <= Np: the chunk's rows are rows of the factor
+        cp.nPm = (int)(cp.Mp / TGP_PW);
+        cp.c0 = r0;
+        const int64_t np = cp.nP - (r0 >> 8);                   // panels the chunk stores
+        if (r0 > 0) TGP_HIP(hipEventRecord(ctx->ev[0], st));
+        TGP_HIP(hipMemsetAsync(cp.d_Bt, 0, (size_t)cp.Mp * np * TGP_PW * 8, st));
+        ident_chunk_kernel<<<(unsigned)(cp.Mp / 256), 256, 0, st>>>(cp.d_Bt, cp.Mp, r0);
+        rc = cov_substitute(ctx, f, cp, true);
+        if (rc) return rc;
+        // kss = nullptr, amp = 0: var_rows_kernel leaves 0 - |row|^2, negated exactly on the host
+        var_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(cp.d_Bt, cp.Mp, (int)np, rows, nullptr, 0.0, cp.d_v);
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipEventRecord(ctx->ev[1], st));
+        TGP_HIP(hipMemcpyAsync(d + r0, cp.d_v, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipEventRecord(ctx->ev[2], st));
+        TGP_HIP(hipStreamSynchronize(st));
+        float ms = 0.f;
+        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        t_dev += ms;
+        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+        t_d2h += ms;
+    }
+    for (int64_t i = 0; i < n; ++i) d[i] = -d[i];
+    ctx->timings[3] = t_dev;                    // device compute
+    ctx->timings[9] = t_d2h;                    // (n) result to the caller's buffer
+    return 0;
 }
 
 // ---- gradient of the log marginal likelihood (kernel derivative convention of treegp/kernels.py:128-150) ------------

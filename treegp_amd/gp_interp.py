@@ -15,6 +15,7 @@ from sklearn.neighbors import KNeighborsRegressor
 from . import ops
 from .fits_io import read_bintable_row
 from .kernels import eval_kernel, kernel_to_spec
+from .loo import loo_quantities
 
 
 class GPInterpolation(object):
@@ -117,6 +118,41 @@ class GPInterpolation(object):
             h.update(arr.tobytes())
         return h.digest()
 
+    @staticmethod
+    def _dense_fingerprint(kernel, X1, y_err):
+        import hashlib
+        h = hashlib.blake2b(digest_size=16)
+        h.update(repr(kernel).encode())
+        h.update(np.asarray(kernel.theta, dtype=np.float64).tobytes())
+        for arr in (X1, y_err):
+            arr = np.ascontiguousarray(arr, dtype=np.float64)
+            h.update(str(arr.shape).encode())
+            h.update(arr.tobytes())
+        return h.digest()
+
+    def _ensure_solution(self, y, X1, kernel, spec, y_err, want_factor):
+        """The cached ``_alpha`` (solved for when None) and, for want_factor, a kept factor of K + diag(y_err^2) that matches
+        its fingerprint.  spec: the device description of the kernel, None for the dense route (scikit-learn evaluates K).
+        The reference caches only alpha (computed when it is None, whatever the arguments: gp_interp.py:179) and rebuilds
+        K + diag(y_err^2) from its ARGUMENTS for every covariance request (:186-187).  The factor kept on the device therefore
+        carries the fingerprint of what it was built from and is rebuilt when that differs; alpha stays the cached one."""
+        if spec is not None:
+            key = self._factor_fingerprint(spec, X1, y_err) if want_factor else None
+            if self._alpha is None:
+                self._alpha, _, _, factor = ops.gp_solve(spec, X1, y, y_err, keep=want_factor)
+                self._set_factor(factor, key)
+            elif want_factor and (self._factor is None or self._factor_key != key):
+                factor = ops.gp_solve(spec, X1, y, y_err, keep=True)[3]
+                self._set_factor(factor, key)
+            return
+        key = self._dense_fingerprint(kernel, X1, y_err) if want_factor else None
+        need_alpha = self._alpha is None
+        if need_alpha or (want_factor and (self._factor is None or self._factor_key != key)):
+            alpha, _, _, factor = ops.gp_solve_dense(kernel(X1), y, y_err, keep=want_factor)
+            if need_alpha:
+                self._alpha = alpha
+            self._set_factor(factor, key)
+
     # -- prediction ------------------------------------------------------------------------------
     def predict(self, X, return_cov=False, return_var=False):
         """Interpolated values (and optionally the posterior covariance) at X (n_samples, 1 or 2).
@@ -145,17 +181,7 @@ class GPInterpolation(object):
             # any other scikit-learn kernel tree (Sum, WhiteKernel, Matern, ...): the kernel object evaluates itself on
             # the host, exactly as in the reference, and the device factorises what it returns (tgp_gp_solve_dense)
             return self._return_gp_predict_dense(y, X1, X2, kernel, y_err, return_cov, return_var)
-        # The reference caches only alpha (computed when it is None, whatever the arguments: gp_interp.py:179) and
-        # rebuilds K + diag(y_err^2) from its ARGUMENTS for every covariance request (:186-187).  The factor kept on the
-        # device therefore carries the fingerprint of what it was built from and is rebuilt when that differs.
-        want_factor = return_cov or return_var
-        key = self._factor_fingerprint(spec, X1, y_err) if want_factor else None
-        if self._alpha is None:
-            self._alpha, _, _, factor = ops.gp_solve(spec, X1, y, y_err, keep=want_factor)
-            self._set_factor(factor, key)
-        elif want_factor and (self._factor is None or self._factor_key != key):
-            factor = ops.gp_solve(spec, X1, y, y_err, keep=True)[3]          # alpha stays the cached one, as in the reference
-            self._set_factor(factor, key)
+        self._ensure_solution(y, X1, kernel, spec, y_err, want_factor=return_cov or return_var)
         y_predict = ops.gp_predict(spec, X1, self._alpha, X2)
         if return_cov:
             y_cov = ops.gp_predict_cov(spec, self._factor, X1, X2)
@@ -169,24 +195,7 @@ class GPInterpolation(object):
         on the host; factorisation, solve and the posterior covariance run on the device.  For return_var the diagonal
         of k(X2) is ``kernel.diag(X2)`` (WhiteKernel's noise included, as in diag(kernel(X2)))."""
         HT = kernel(X2, Y=X1)
-        want_factor = return_cov or return_var
-        key = None
-        if want_factor:
-            import hashlib
-            h = hashlib.blake2b(digest_size=16)
-            h.update(repr(kernel).encode())
-            h.update(np.asarray(kernel.theta, dtype=np.float64).tobytes())
-            for arr in (X1, y_err):
-                arr = np.ascontiguousarray(arr, dtype=np.float64)
-                h.update(str(arr.shape).encode())
-                h.update(arr.tobytes())
-            key = h.digest()
-        need_alpha = self._alpha is None
-        if need_alpha or (want_factor and (self._factor is None or self._factor_key != key)):
-            alpha, _, _, factor = ops.gp_solve_dense(kernel(X1), y, y_err, keep=want_factor)
-            if need_alpha:
-                self._alpha = alpha
-            self._set_factor(factor, key)
+        self._ensure_solution(y, X1, kernel, None, y_err, want_factor=return_cov or return_var)
         y_predict = np.dot(HT, self._alpha.reshape((len(self._alpha), 1))).T[0]
         if return_cov:
             return y_predict, ops.gp_predict_cov_dense(self._factor, HT, kernel(X2))
@@ -242,6 +251,90 @@ class GPInterpolation(object):
             else:
                 pred = alphas.dot(self.kernel(X, Y=self._X).T)
         return pred + means[:, None] + self._build_average_meanify(X)[None, :]
+
+    # -- leave-one-out (not in the reference) ----------------------------------------------------
+    def predict_loo(self, return_var=False):
+        """Leave-one-out predictions at the positions given to ``initialize``: entry i is what ``predict(X[i:i+1],
+        return_var=True)`` returns for a GP with the same kernel given the other n - 1 points, in closed form from alpha and
+        diag(K^-1) (Rasmussen & Williams 5.4.2; ops.factor_inv_diag, ~n^3 / 3 flops on the device) instead of n refits.
+        ``_mean`` and the mean function are held at their full-data values (R&W treat them as fixed).  Returns y_loo (n,),
+        or (y_loo, var_loo) with var_loo the latent variance 1 / d_i - sigma_i^2, not clamped at zero, as ``return_var``.
+        Uses the cached ``_alpha`` and the kept factor under the same rules as ``predict(..., return_var=True)``: either
+        reuses what the other left; any kernel tree works (the dense route keeps a factor as well)."""
+        r = self._residual()
+        try:
+            spec = kernel_to_spec(self.kernel)
+        except NotImplementedError:
+            spec = None
+        with self._scope():
+            self._ensure_solution(r, self._X, self.kernel, spec, self._y_err, want_factor=True)
+            d = ops.factor_inv_diag(self._factor)
+        mu, _, v, _ = loo_quantities(r, self._alpha, d, self._y_err)
+        y_loo = mu + self._mean + self._spatial_average
+        return (y_loo, v) if return_var else y_loo
+
+    def return_loo_log_predictive(self, theta=None):
+        """sum_i log p(y_i | y_-i) (Rasmussen & Williams eq. 5.11) for the current (or the given) hyper-parameters: a held-out
+        score of the fit, comparable between optimisers.  Mirrors ``return_log_likelihood``: a temporary factor of its own,
+        ``_alpha`` and the kept factor are left untouched; -inf when the factorisation fails."""
+        from ._lib import TgpError
+        from .log_likelihood import _rejects_theta
+        kernel = copy.deepcopy(self.kernel)
+        if theta is not None:
+            kernel = kernel.clone_with_theta(theta)
+        r = self._residual()
+        try:
+            spec = kernel_to_spec(kernel)
+        except NotImplementedError:
+            spec = None
+        try:
+            with self._scope():
+                if spec is not None:
+                    alpha, _, _, factor = ops.gp_solve(spec, self._X, r, self._y_err, keep=True)
+                else:
+                    alpha, _, _, factor = ops.gp_solve_dense(kernel(self._X), r, self._y_err, keep=True)
+                try:
+                    d = ops.factor_inv_diag(factor)
+                finally:
+                    factor.free(keep_memory=True)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                total = float(np.sum(loo_quantities(r, alpha, d, self._y_err)[3]))
+        except (np.linalg.LinAlgError, FloatingPointError, ValueError):
+            total = -np.inf                    # as log_likelihood (log_likelihood.py:38-39 of the reference)
+        except TgpError as ex:
+            if not _rejects_theta(ex):
+                raise
+            total = -np.inf
+        return total if np.isfinite(total) else -np.inf
+
+    def predict_fields_loo(self, Y, y_err=None):
+        """Leave-one-out predictions of several fields measured at the positions given to ``initialize`` (the
+        ``predict_fields`` pattern): Y (n_fields, n) -> (n_fields, n).  One factorisation, one diag(K^-1) and one multi-
+        right-hand-side solve serve all fields; every field keeps its own mean (``normalize``), held fixed as in
+        ``predict_loo``, and shares the mean function, the kernel and the errors.  ``_alpha`` and the kept factor are left
+        untouched."""
+        Y = np.atleast_2d(np.asarray(Y, dtype=np.float64))
+        if Y.ndim != 2 or Y.shape[1] != len(self._X):
+            raise ValueError("Y must be (n_fields, %d)" % len(self._X))
+        sigma = self._y_err if y_err is None else np.sqrt(np.asarray(y_err, dtype=np.float64) ** 2 + self.white_noise ** 2)
+        means = np.mean(Y - self._spatial_average, axis=1) if self.normalize else np.zeros(len(Y))
+        R = Y - means[:, None] - self._spatial_average[None, :]
+        try:
+            spec = kernel_to_spec(self.kernel)
+        except NotImplementedError:
+            spec = None
+        with self._scope():
+            if spec is not None:
+                _, _, _, factor = ops.gp_solve(spec, self._X, R[0], sigma, keep=True, want_alpha=False)
+            else:
+                _, _, _, factor = ops.gp_solve_dense(self.kernel(self._X), R[0], sigma, keep=True, want_alpha=False)
+            try:
+                alphas = ops.factor_solve(factor, R)
+                d = ops.factor_inv_diag(factor)
+            finally:
+                factor.free(keep_memory=True)
+        mu = loo_quantities(R, alphas, d, sigma)[0]
+        return mu + means[:, None] + self._spatial_average[None, :]
 
     # -- data ------------------------------------------------------------------------------------
     def initialize(self, X, y, y_err=None):

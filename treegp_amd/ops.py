@@ -228,6 +228,19 @@ def factor_lmul(factor, Z, ctx=None):
     return out
 
 
+def factor_inv_diag(factor, ctx=None):
+    """diag((K + D)^-1) (n,) from a kept factor (tgp_factor_inv_diag): |L^-1 e_i|^2 for every i, identity rows substituted on
+    the device in chunks (~n^3 / 3 flops, no n x n buffer on either side).  With alpha = (K + D)^-1 r it gives every point's
+    leave-one-out prediction (treegp_amd.loo.loo_quantities)."""
+    if factor is None or not factor._h:
+        raise ValueError("factor_inv_diag needs a kept factor (gp_solve(..., keep=True)) that has not been freed")
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    d = np.empty(factor.n)
+    check(ctx, lib.tgp_factor_inv_diag(ctx, factor._h, ptr(d)), "tgp_factor_inv_diag")
+    return d
+
+
 def gp_predict_cov_dense(factor, HT, Kss, ctx=None):
     """Kss - HT (K + D)^-1 HT^T for caller-evaluated HT = kernel(X2, Y=X1) (m, n) and Kss = kernel(X2) (m, m)."""
     ctx = ctx or factor._ctx
