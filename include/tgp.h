@@ -12,6 +12,7 @@
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
  *   S3d realisations y = L z             np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66, 95-97
  *   S3e diag(K^-1) of a kept factor      not in the reference: leave-one-out residuals and variances (R&W 5.4.2)
+ *   S3f many small S3b / S3c at once    treegp/gp_interp.py:184-192 for the problems of S2e, README.rst:28
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
  *   S6  binned_statistic_2d              treegp/meanify.py:76-107
@@ -166,6 +167,25 @@ int tgp_gp_predict_var(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const d
 /* the same with HT = kernel(X2, Y=X1) (m, n) and kss = kernel.diag(X2) (m) evaluated by the caller */
 int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const double *HT, const double *kss,
                              int64_t m, double *var);
+
+/* ---- S3f: S3b / S3c for the nb problems of S2e, from their factors, in the same call ------------------------------------
+ * Every reference test and the documented usage call predict(X, return_cov=True) (treegp/gp_interp.py:184-192); with one GP
+ * per PSF parameter, exposure or chip (README.rst:28) that is one factorisation and one substitution per object.  Here the
+ * batch of S2e is factorised as tgp_gp_solve_batch does it and, in the same chunk, each problem's factor gives the posterior at
+ * its ms[b] query points Xs (nb, mmax, 2) (rows >= ms[b] are not read): what = 1, unc (nb, mmax) = the variance as S3c;
+ * what = 2, unc (nb, mmax, mmax) = the covariance as S3b.  Every entry outside ms[b] (variance) or ms[b] x ms[b] (covariance)
+ * is exactly 0.  ks, ns, nmax, X, y, yerr, alpha, logdet, ydota and info as tgp_gp_solve_batch, bit for bit; a problem with
+ * info[b] > 0 has meaningless outputs and the others are unaffected, bit for bit.  A problem's bits depend neither on its
+ * companions, nor on its place in the batch, nor on the chunking (TGP_BATCH_CHUNK, as S2e; the chunk also holds Bt (Mp x Np,
+ * Mp = mmax rounded up to 256) and, for the covariance, an Mp x Mp matrix per problem).  Not clamped at zero.
+ * Limits: 1 <= ms[b] <= mmax; mmax <= 4096 for the covariance, <= 65 280 for the variance; nmax, ns and kinds as S2e.
+ * Returns 0 when every problem was attempted; -1 with a message naming the entry for out-of-range arguments or an unknown
+ * `what`; -2 for HIP errors.  Timings [0] K build, [1] Cholesky, [2] sweeps and logdet, [3] posterior device compute,
+ * [9] result transfer, summed over the chunks; every other slot 0.                                                          */
+int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+                           const double *X, const double *y, const double *yerr,
+                           const int64_t *ms, int64_t mmax, const double *Xs, int what,
+                           double *alpha, double *unc, double *logdet, double *ydota, int32_t *info);
 
 /* ---- S3d: realisations -- Yout[v] = L Z[v], L the lower Cholesky factor of K + diag(yerr^2) kept by tgp_gp_solve /
  * tgp_gp_solve_dense (stands in for np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66,95-97 of

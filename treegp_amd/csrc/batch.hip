@@ -207,13 +207,123 @@ __global__ __launch_bounds__(256) void bfinish_kernel(const double *__restrict__
     }
 }
 
+// ---- posterior of every problem (seam S3f): S3b / S3c of cov.hip with the problem index on the grid -------------------------
+// Problem b's query rows live in the 256-wide panel layout of cov.hip's Bt: Bt_b (Mp x Np) at b * Mp * Np, panel p at
+// + p * Mp * 256; the covariance's C_b (Mp x Mp) at b * Mp * Mp in the same layout.  Tile forms and summation depths depend on
+// kb, Np and Mp only.  Row tiles at or beyond m_b and column blocks at or beyond n_b are zero from the start and stay zero, so a
+// problem skips them: its own sizes decide which, never its companions'.
+struct PostDims {
+    int64_t Mp;
+    int64_t mmax;
+};
+
+// H_b = amp_b k_b(Xs_b, X_b) (self: k_b(Xs_b, Xs_b), diagonal exactly amp_b): rows < m_b, columns < ncols_b, zero elsewhere.
+// Every element of the Mp x ncols panels is written.  blockIdx.x = 256-column group + (ncols / 256) * row, blockIdx.y = the
+// y-th problem of this evaluator.  Xs: the caller's (nb, mmax, 2) rows, read below m_b only; X: the staged (nb, Np, 2).
+template <int KE>
+__global__ __launch_bounds__(256) void bcross_kernel(const KParams *__restrict__ kp, const int *__restrict__ list,
+                                                     const int64_t *__restrict__ ns, const int64_t *__restrict__ ms,
+                                                     const double *__restrict__ Xs, const double *__restrict__ X, int64_t Np,
+                                                     PostDims q, int self, int64_t ncols, double *__restrict__ out) {
+    const int b = list[blockIdx.y];
+    const int64_t ng = ncols / 256;
+    const int64_t i = blockIdx.x / ng;
+    const int64_t j = (blockIdx.x % ng) * 256 + threadIdx.x;
+    const int64_t m = ms[b], n = self ? m : ns[b];
+    const double *xs = Xs + (int64_t)b * 2 * q.mmax;
+    const double *x = self ? xs : X + (int64_t)b * 2 * Np;
+    const KParams p = kp[b];
+    double v = 0.0;
+    if (i < m && j < n) {
+        v = kernel_value<KE>(p, xs[2 * i] - x[2 * j], xs[2 * i + 1] - x[2 * j + 1]);
+        if (self && i == j) v = p.amp;
+    }
+    out[(int64_t)b * q.Mp * ncols + (j >> 8) * q.Mp * TGP_PW + i * TGP_PW + (j & 255)] = v;
+}
+
+// Bt_b[:, kb] <- Bt_b[:, kb] W_kb^T, one 128-row tile per workgroup (cov_trsm_kernel)
+__global__ __launch_bounds__(256, 2) void btrsm_kernel(double *Bt, const double *W, const int64_t *__restrict__ ns,
+                                                       const int64_t *__restrict__ ms, BatchDims d, PostDims q, int kb) {
+    const int b = blockIdx.y;
+    const int64_t t = blockIdx.x;
+    if (t * TGP_TB >= ms[b] || (int64_t)kb * TGP_TB >= ns[b]) return;
+    double *Bk = Bt + (int64_t)b * q.Mp * d.Np + (int64_t)(kb >> 1) * q.Mp * TGP_PW + (kb & 1) * TGP_TB + t * TGP_TB * TGP_PW;
+    gemm_tile_128<0, TGP_TB, TGP_TB>(Bk, W + b * d.we + (int64_t)kb * TGP_TB * TGP_TB, Bk);
+}
+
+// Bt_b[:, c] -= Bt_b[:, kb] L_b[c, kb]^T for c = kb + 1 + blockIdx.x / mt, row tile blockIdx.x % mt (cov_update_kernel)
+__global__ __launch_bounds__(256, 2) void bupdate_kernel(double *Bt, const double *A, const int64_t *__restrict__ ns,
+                                                         const int64_t *__restrict__ ms, BatchDims d, PostDims q, int kb, int mt) {
+    const int b = blockIdx.y;
+    const int64_t ti = blockIdx.x % mt;
+    const int64_t c = kb + 1 + blockIdx.x / mt;
+    if (ti * TGP_TB >= ms[b] || c * TGP_TB >= ns[b]) return;
+    const int64_t p = kb >> 1;
+    double *Btb = Bt + (int64_t)b * q.Mp * d.Np;
+    const double *a = Btb + p * q.Mp * TGP_PW + ti * TGP_TB * TGP_PW + (kb & 1) * TGP_TB;
+    const double *l = A + b * d.ae + panel_off(p, d.Np) + (c * TGP_TB - p * TGP_PW) * TGP_PW + (kb & 1) * TGP_TB;
+    double *cc = Btb + (c >> 1) * q.Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
+    gemm_tile_dtv<4, TGP_TB, 1>(a, l, cc, nullptr, nullptr);
+}
+
+// var_b[i] = amp_b - |Bt_b[i, :]|^2 over all Np / 256 panels, one wave per row as var_rows_kernel; rows >= m_b are 0
+__global__ __launch_bounds__(256) void bvar_rows_kernel(const double *__restrict__ Bt, const KParams *__restrict__ kp,
+                                                        const int64_t *__restrict__ ms, int64_t Np, PostDims q,
+                                                        double *__restrict__ var) {
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= q.mmax) return;                                     // whole waves leave together
+    double *out = var + (int64_t)b * q.mmax + i;
+    if (i >= ms[b]) {
+        if (lane == 0) *out = 0.0;
+        return;
+    }
+    const int nP = (int)(Np / TGP_PW);
+    const double *row = Bt + (int64_t)b * q.Mp * Np + i * TGP_PW + 2 * lane;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int p = 0; p < nP; ++p) {
+        const double2 a = *(const double2 *)(row + (int64_t)p * q.Mp * TGP_PW);
+        const double2 c = *(const double2 *)(row + (int64_t)p * q.Mp * TGP_PW + 128);
+        acc += (a.x * a.x + a.y * a.y) + (c.x * c.x + c.y * c.y);
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if (lane == 0) *out = kp[b].amp - acc;
+}
+
+// C_b(ti, tj) -= sum over all panels of Bt_b[ti] Bt_b[tj]^T (cov_syrk_kernel); blockIdx.x = ti + mt * tj
+__global__ __launch_bounds__(256, 2) void bsyrk_cov_kernel(double *C, const double *Bt, const int64_t *__restrict__ ms, int64_t Np,
+                                                           PostDims q, int mt) {
+    const int b = blockIdx.y;
+    const int64_t ti = blockIdx.x % mt, tj = blockIdx.x / mt;
+    if (ti * TGP_TB >= ms[b] || tj * TGP_TB >= ms[b]) return;
+    const double *Btb = Bt + (int64_t)b * q.Mp * Np;
+    double *c = C + (int64_t)b * q.Mp * q.Mp + (tj >> 1) * q.Mp * TGP_PW + ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
+    gemm_tile_dtv<4, TGP_PW, 0>(Btb + ti * TGP_TB * TGP_PW, Btb + tj * TGP_TB * TGP_PW, c, nullptr, nullptr, (int)(Np / TGP_PW),
+                                q.Mp * TGP_PW, q.Mp * TGP_PW);
+}
+
+// C_b (panels) -> the caller's (nb, mmax, mmax), exactly 0 outside m_b x m_b; blockIdx.x = 256-column group + groups * row
+__global__ __launch_bounds__(256) void bunpad_cov_kernel(const double *__restrict__ C, const int64_t *__restrict__ ms, PostDims q,
+                                                         double *__restrict__ out) {
+    const int b = blockIdx.y;
+    const int64_t ng = (q.mmax + 255) / 256;
+    const int64_t i = blockIdx.x / ng;
+    const int64_t j = (blockIdx.x % ng) * 256 + threadIdx.x;
+    if (j >= q.mmax) return;
+    const int64_t m = ms[b];
+    out[((int64_t)b * q.mmax + i) * q.mmax + j] =
+        (i < m && j < m) ? C[(int64_t)b * q.Mp * q.Mp + (j >> 8) * q.Mp * TGP_PW + i * TGP_PW + (j & 255)] : 0.0;
+}
+
 inline size_t rup(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
 // problems per chunk: TGP_BATCH_CHUNK, or as many as 90 % of the free device memory holds (the context's own scratch counted as
 // free: it is given back before a bigger one is taken)
-static int64_t batch_chunk(tgp_ctx *ctx, int nb, size_t per, size_t fixed, int *rc) {
+static int64_t batch_chunk(tgp_ctx *ctx, const char *fn, int nb, size_t per, size_t fixed, int *rc) {
     *rc = 0;
     const char *e = getenv("TGP_BATCH_CHUNK");                // read per call, as TGP_VAR_CHUNK is
     if (e && atoi(e) > 0) {
@@ -232,142 +342,208 @@ static int64_t batch_chunk(tgp_ctx *ctx, int nb, size_t per, size_t fixed, int *
     if (c > nb) c = nb;
     if (c > 65535) c = 65535;                                   // the problem index is a grid's y dimension
     if (c < 1) {
-        ctx->err = "tgp_gp_solve_batch: not enough free device memory for one problem of this order";
+        ctx->err = std::string(fn) + ": not enough free device memory for one problem of this order";
         *rc = -2;
     }
     return c;
 }
 
-int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
-                       const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
-    if (!ctx) return -1;
-    if (nb < 1) { ctx->err = "tgp_gp_solve_batch: nb must be >= 1"; return -1; }
-    if (nmax < 1 || nmax > 4096) { ctx->err = "tgp_gp_solve_batch: nmax must be in 1 .. 4096 (larger problems: tgp_gp_solve)"; return -1; }
-    TGP_ARG(ks && ns && X && y && logdet && info);
+// nb, nmax, ns[b] and the kinds, as both batched entries take them; -1 with a message naming `fn`
+static int batch_check(tgp_ctx *ctx, const char *fn, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax) {
+    const std::string f(fn);
+    if (nb < 1) { ctx->err = f + ": nb must be >= 1"; return -1; }
+    if (nmax < 1 || nmax > 4096) { ctx->err = f + ": nmax must be in 1 .. 4096 (larger problems: tgp_gp_solve)"; return -1; }
     for (int b = 0; b < nb; ++b) {
         if (ns[b] < 1 || ns[b] > nmax) {
-            ctx->err = "tgp_gp_solve_batch: ns[" + std::to_string(b) + "] = " + std::to_string((long long)ns[b]) + " is not in 1 .. nmax = " +
+            ctx->err = f + ": ns[" + std::to_string(b) + "] = " + std::to_string((long long)ns[b]) + " is not in 1 .. nmax = " +
                        std::to_string((long long)nmax);
             return -1;
         }
         if (kind_to_ke(ks[b].kind) < 0) {
-            ctx->err = "tgp_gp_solve_batch: ks[" + std::to_string(b) + "].kind = " + std::to_string(ks[b].kind) + " is not a kernel kind";
+            ctx->err = f + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks[b].kind) + " is not a kernel kind";
             return -1;
         }
     }
-    TGP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW, nT = Np / TGP_TB;
-    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
-    const size_t per = rup((size_t)d.ae * 8) + rup((size_t)d.we * 8) + 6 * rup((size_t)Np * 8) + 5 * rup((size_t)nmax * 8) +
-                       rup(sizeof(KParams)) + 2 * rup(8) + 2 * rup(16);
-    const size_t fixed = 8 * 256;
-    int rc = 0;
-    const int64_t C = batch_chunk(ctx, nb, per, fixed, &rc);
-    if (rc) return rc;
-    // one arena per chunk size: arrays of C problems each
-    const size_t need = (size_t)C * per + fixed;
-    rc = tgp_ensure_scratch(ctx, need);
-    if (rc) return rc;
-    char *base = (char *)ctx->scratch;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { void *p = base + off; off += rup(bytes); return p; };
-    double *dA = (double *)take((size_t)C * d.ae * 8);
-    double *dW = (double *)take((size_t)C * d.we * 8);
-    double *dX = (double *)take((size_t)C * 2 * Np * 8);
-    double *dy = (double *)take((size_t)C * Np * 8);
-    double *de = (double *)take((size_t)C * Np * 8);
-    double *dz = (double *)take((size_t)C * Np * 8);
-    double *da = (double *)take((size_t)C * Np * 8);
-    double *rX = (double *)take((size_t)C * 2 * nmax * 8);
-    double *ry = (double *)take((size_t)C * nmax * 8);
-    double *re = (double *)take((size_t)C * nmax * 8);
-    double *ra = (double *)take((size_t)C * nmax * 8);
-    KParams *dkp = (KParams *)take((size_t)C * sizeof(KParams));
-    int64_t *dns = (int64_t *)take((size_t)C * 8);
-    int *dlist = (int *)take((size_t)C * 4);
-    int *dinfo = (int *)take((size_t)C * 4);
-    double *dout = (double *)take((size_t)C * 16);
+    return 0;
+}
+
+// the per-problem arrays of one chunk of S2e (device arena + pinned host tables); the posterior's own arrays follow them
+struct BatchBufs {
+    double *dA, *dW, *dX, *dy, *de, *dz, *da, *rX, *ry, *re, *ra, *dout;
+    KParams *dkp;
+    int64_t *dns;
+    int *dlist, *dinfo;
+    KParams *hkp;
+    int64_t *hns;
+    int *hlist, *hinfo;
+    double *hout;
+    int cnt[3], start[3];          // the chunk's evaluator lists: problems per evaluator and where each starts in dlist
+};
+
+static size_t batch_bytes_per_problem(const BatchDims &d, int64_t nmax) {
+    return rup((size_t)d.ae * 8) + rup((size_t)d.we * 8) + 6 * rup((size_t)d.Np * 8) + 5 * rup((size_t)nmax * 8) +
+           rup(sizeof(KParams)) + 2 * rup(8) + 2 * rup(16);
+}
+
+// carves C problems' arrays of S2e out of the arena at `base` (+ *off) and the pinned host scratch
+static int batch_take(tgp_ctx *ctx, const BatchDims &d, int64_t nmax, int64_t C, char *base, size_t *off, BatchBufs *bb) {
+    auto take = [&](size_t bytes) { void *p = base + *off; *off += rup(bytes); return p; };
+    const int64_t Np = d.Np;
+    bb->dA = (double *)take((size_t)C * d.ae * 8);
+    bb->dW = (double *)take((size_t)C * d.we * 8);
+    bb->dX = (double *)take((size_t)C * 2 * Np * 8);
+    bb->dy = (double *)take((size_t)C * Np * 8);
+    bb->de = (double *)take((size_t)C * Np * 8);
+    bb->dz = (double *)take((size_t)C * Np * 8);
+    bb->da = (double *)take((size_t)C * Np * 8);
+    bb->rX = (double *)take((size_t)C * 2 * nmax * 8);
+    bb->ry = (double *)take((size_t)C * nmax * 8);
+    bb->re = (double *)take((size_t)C * nmax * 8);
+    bb->ra = (double *)take((size_t)C * nmax * 8);
+    bb->dkp = (KParams *)take((size_t)C * sizeof(KParams));
+    bb->dns = (int64_t *)take((size_t)C * 8);
+    bb->dlist = (int *)take((size_t)C * 4);
+    bb->dinfo = (int *)take((size_t)C * 4);
+    bb->dout = (double *)take((size_t)C * 16);
     // host side of the small tables and results: the context's pinned scratch
     const size_t hbytes = rup((size_t)C * sizeof(KParams)) + rup((size_t)C * 8) + rup((size_t)C * 4) + rup((size_t)C * 4) + rup((size_t)C * 16);
     void *hp = nullptr;
-    rc = tgp_ensure_pinned(ctx, hbytes, &hp);
+    int rc = tgp_ensure_pinned(ctx, hbytes, &hp);
     if (rc) return rc;
     char *hb = (char *)hp;
-    KParams *hkp = (KParams *)hb;
-    int64_t *hns = (int64_t *)(hb + rup((size_t)C * sizeof(KParams)));
-    int *hlist = (int *)((char *)hns + rup((size_t)C * 8));
-    int *hinfo = (int *)((char *)hlist + rup((size_t)C * 4));
-    double *hout = (double *)((char *)hinfo + rup((size_t)C * 4));
-
+    bb->hkp = (KParams *)hb;
+    bb->hns = (int64_t *)(hb + rup((size_t)C * sizeof(KParams)));
+    bb->hlist = (int *)((char *)bb->hns + rup((size_t)C * 8));
+    bb->hinfo = (int *)((char *)bb->hlist + rup((size_t)C * 4));
+    bb->hout = (double *)((char *)bb->hinfo + rup((size_t)C * 4));
     static bool attr_ok = hipFuncSetAttribute((const void *)bpotrf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)potrf_v2::POTRF_LDS_BYTES) == hipSuccess;
-    if (!attr_ok) { ctx->err = "tgp_gp_solve_batch: the diagonal-block kernel cannot have its LDS image"; return -2; }
+    if (!attr_ok) { ctx->err = "batched solve: the diagonal-block kernel cannot have its LDS image"; return -2; }
+    return 0;
+}
+
+// problems c0 .. c0 + cn of the batch: staging, K build, factorisation, sweeps and logdet / chi2, on the context's stream; alpha
+// (padded, Np) in bb.da and unpadded in bb.ra when `want_alpha`.  Events: ev[0] .. ev[1] K build, .. ev[2] Cholesky, .. ev[3]
+// sweeps.  Nothing is copied back and the stream is not synchronised.
+static int batch_factor_chunk(tgp_ctx *ctx, const BatchDims &d, BatchBufs &bb, int64_t c0, int64_t cn, const tgp_kernel *ks,
+                              const int64_t *ns, int64_t nmax, const double *X, const double *y, const double *yerr, bool want_alpha) {
+    hipStream_t st = ctx->stream;
+    const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
+    // evaluator lists: the problems of this chunk grouped by kernel evaluator, each group in batch order
+    int *cnt = bb.cnt, *start = bb.start;
+    cnt[0] = cnt[1] = cnt[2] = 0;
+    for (int64_t b = 0; b < cn; ++b) {
+        bb.hkp[b] = make_kparams(&ks[c0 + b]);
+        bb.hns[b] = ns[c0 + b];
+        ++cnt[kind_to_ke(ks[c0 + b].kind)];
+    }
+    start[0] = 0;
+    start[1] = cnt[0];
+    start[2] = cnt[0] + cnt[1];
+    int fill[3] = {0, 0, 0};
+    for (int64_t b = 0; b < cn; ++b) {
+        const int k = kind_to_ke(ks[c0 + b].kind);
+        bb.hlist[start[k] + fill[k]++] = (int)b;
+    }
+    TGP_HIP(hipMemcpyAsync(bb.dkp, bb.hkp, (size_t)cn * sizeof(KParams), hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(bb.dns, bb.hns, (size_t)cn * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(bb.dlist, bb.hlist, (size_t)cn * 4, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(bb.rX, X + c0 * nmax * 2, (size_t)cn * nmax * 16, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(bb.ry, y + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
+    if (yerr) TGP_HIP(hipMemcpyAsync(bb.re, yerr + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemsetAsync(bb.dinfo, 0, (size_t)cn * 4, st));
+    const unsigned ncn = (unsigned)cn;
+    double *dA = bb.dA, *dW = bb.dW;
+    bpad_kernel<<<dim3((unsigned)(Np / 256), ncn), 256, 0, st>>>(bb.rX, bb.ry, yerr ? bb.re : nullptr, bb.dns, nmax, Np, bb.dX, bb.dy,
+                                                                 yerr ? bb.de : nullptr);
+    const double *e_or_null = yerr ? bb.de : nullptr;
+
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    const unsigned ntiles = (unsigned)(nT * (nT + 1) / 2);
+    if (cnt[0]) bkbuild_kernel<KE_GAUSS><<<dim3(ntiles, cnt[0]), 256, 0, st>>>(bb.dkp, bb.dlist + start[0], bb.dns, bb.dX, e_or_null, d, dA);
+    if (cnt[1]) bkbuild_kernel<KE_VK><<<dim3(ntiles, cnt[1]), 256, 0, st>>>(bb.dkp, bb.dlist + start[1], bb.dns, bb.dX, e_or_null, d, dA);
+    if (cnt[2]) bkbuild_kernel<KE_AVK><<<dim3(ntiles, cnt[2]), 256, 0, st>>>(bb.dkp, bb.dlist + start[2], bb.dns, bb.dX, e_or_null, d, dA);
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+
+    // right-looking, one 256-wide panel at a time
+    for (int k = 0; k < (int)nP; ++k) {
+        const int64_t pk = panel_off(k, Np), mk = Np - (int64_t)TGP_PW * k;
+        const int64_t w0 = (int64_t)(2 * k) * TGP_TB * TGP_TB, w1 = w0 + TGP_TB * TGP_TB;
+        const int64_t r1 = pk + (int64_t)TGP_TB * TGP_PW;          // row 128 of the panel
+        const unsigned nr1 = (unsigned)((mk - TGP_TB) / TGP_TB), nr2 = (unsigned)((mk - TGP_PW) / TGP_TB);
+        bpotrf_kernel<<<ncn, 256, potrf_v2::POTRF_LDS_BYTES, st>>>(dA, dW, d, pk, w0, bb.dinfo, k * TGP_PW);
+        bgemm_col_kernel<0, TGP_TB, true><<<dim3(nr1, ncn), 256, 0, st>>>(dA, dW, d, r1, w0, r1);
+        bgemm_col_kernel<1, TGP_PW, false><<<dim3(nr1, ncn), 256, 0, st>>>(dA, dW, d, r1, r1, r1 + TGP_TB);
+        bpotrf_kernel<<<ncn, 256, potrf_v2::POTRF_LDS_BYTES, st>>>(dA, dW, d, r1 + TGP_TB, w1, bb.dinfo, k * TGP_PW + TGP_TB);
+        if (nr2 == 0) continue;
+        const int64_t r2 = pk + (int64_t)TGP_PW * TGP_PW + TGP_TB;   // row 256, column 128
+        bgemm_col_kernel<0, TGP_TB, true><<<dim3(nr2, ncn), 256, 0, st>>>(dA, dW, d, r2, w1, r2);
+        bsyrk_kernel<<<dim3((unsigned)(nr2 * (nr2 + 1) / 2), ncn), 256, 0, st>>>(dA, d, k, (int)nr2);
+    }
+    TGP_HIP(hipEventRecord(ctx->ev[2], st));
+
+    for (int j = 0; j < (int)nT; ++j)
+        bfwd_step_kernel<<<dim3((unsigned)(nT - j), ncn), 256, 0, st>>>(dA, dW, d, bb.dy, bb.dz, j);
+    bfinish_kernel<<<ncn, 256, 0, st>>>(dA, bb.dz, bb.dns, d, bb.dout);
+    if (want_alpha) {
+        for (int j = (int)nT - 1; j >= 0; --j)
+            bbwd_step_kernel<<<dim3((unsigned)(j + 1), ncn), 256, 0, st>>>(dA, dW, d, bb.dz, bb.da, j);
+        bunpad_kernel<<<dim3((unsigned)((nmax + 255) / 256), ncn), 256, 0, st>>>(bb.da, bb.dns, nmax, Np, bb.ra);
+    }
+    TGP_HIP(hipEventRecord(ctx->ev[3], st));
+    TGP_HIP(hipGetLastError());
+    return 0;
+}
+
+// after the stream has been synchronised: the chunk's info, logdet and chi2 to the caller's arrays
+static int batch_collect(tgp_ctx *ctx, const char *fn, const BatchBufs &bb, int64_t c0, int64_t cn, double *logdet, double *ydota,
+                         int32_t *info) {
+    for (int64_t b = 0; b < cn; ++b) {
+        if (bb.hinfo[b] < 0) {
+            ctx->err = std::string(fn) + ": a diagonal block of problem " + std::to_string((long long)(c0 + b)) +
+                       " reported an internal hand-off failure (info " + std::to_string(bb.hinfo[b]) + ")";
+            return -2;
+        }
+        info[c0 + b] = bb.hinfo[b];
+        logdet[c0 + b] = bb.hout[2 * b];
+        if (ydota) ydota[c0 + b] = bb.hout[2 * b + 1];
+    }
+    return 0;
+}
+
+int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                       const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
+    static const char *fn = "tgp_gp_solve_batch";
+    if (!ctx) return -1;
+    if (nb < 1) { ctx->err = "tgp_gp_solve_batch: nb must be >= 1"; return -1; }
+    if (nmax < 1 || nmax > 4096) { ctx->err = "tgp_gp_solve_batch: nmax must be in 1 .. 4096 (larger problems: tgp_gp_solve)"; return -1; }
+    TGP_ARG(ks && ns && X && y && logdet && info);
+    int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
+    if (rc) return rc;
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW;
+    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
+    const size_t per = batch_bytes_per_problem(d, nmax);
+    const size_t fixed = 8 * 256;
+    const int64_t C = batch_chunk(ctx, fn, nb, per, fixed, &rc);
+    if (rc) return rc;
+    // one arena per chunk size: arrays of C problems each
+    rc = tgp_ensure_scratch(ctx, (size_t)C * per + fixed);
+    if (rc) return rc;
+    size_t off = 0;
+    BatchBufs bb;
+    rc = batch_take(ctx, d, nmax, C, (char *)ctx->scratch, &off, &bb);
+    if (rc) return rc;
 
     double ms_k = 0.0, ms_c = 0.0, ms_s = 0.0;
     for (int64_t c0 = 0; c0 < nb; c0 += C) {
         const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
-        // evaluator lists: the problems of this chunk grouped by kernel evaluator, each group in batch order
-        int cnt[3] = {0, 0, 0};
-        for (int64_t b = 0; b < cn; ++b) {
-            hkp[b] = make_kparams(&ks[c0 + b]);
-            hns[b] = ns[c0 + b];
-            ++cnt[kind_to_ke(ks[c0 + b].kind)];
-        }
-        int start[3] = {0, cnt[0], cnt[0] + cnt[1]}, fill[3] = {0, 0, 0};
-        for (int64_t b = 0; b < cn; ++b) {
-            const int k = kind_to_ke(ks[c0 + b].kind);
-            hlist[start[k] + fill[k]++] = (int)b;
-        }
-        TGP_HIP(hipMemcpyAsync(dkp, hkp, (size_t)cn * sizeof(KParams), hipMemcpyHostToDevice, st));
-        TGP_HIP(hipMemcpyAsync(dns, hns, (size_t)cn * 8, hipMemcpyHostToDevice, st));
-        TGP_HIP(hipMemcpyAsync(dlist, hlist, (size_t)cn * 4, hipMemcpyHostToDevice, st));
-        TGP_HIP(hipMemcpyAsync(rX, X + c0 * nmax * 2, (size_t)cn * nmax * 16, hipMemcpyHostToDevice, st));
-        TGP_HIP(hipMemcpyAsync(ry, y + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
-        if (yerr) TGP_HIP(hipMemcpyAsync(re, yerr + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
-        TGP_HIP(hipMemsetAsync(dinfo, 0, (size_t)cn * 4, st));
-        const unsigned ncn = (unsigned)cn;
-        bpad_kernel<<<dim3((unsigned)(Np / 256), ncn), 256, 0, st>>>(rX, ry, yerr ? re : nullptr, dns, nmax, Np, dX, dy,
-                                                                     yerr ? de : nullptr);
-        const double *e_or_null = yerr ? de : nullptr;
-
-        TGP_HIP(hipEventRecord(ctx->ev[0], st));
-        const unsigned ntiles = (unsigned)(nT * (nT + 1) / 2);
-        if (cnt[0]) bkbuild_kernel<KE_GAUSS><<<dim3(ntiles, cnt[0]), 256, 0, st>>>(dkp, dlist + start[0], dns, dX, e_or_null, d, dA);
-        if (cnt[1]) bkbuild_kernel<KE_VK><<<dim3(ntiles, cnt[1]), 256, 0, st>>>(dkp, dlist + start[1], dns, dX, e_or_null, d, dA);
-        if (cnt[2]) bkbuild_kernel<KE_AVK><<<dim3(ntiles, cnt[2]), 256, 0, st>>>(dkp, dlist + start[2], dns, dX, e_or_null, d, dA);
-        TGP_HIP(hipEventRecord(ctx->ev[1], st));
-
-        // right-looking, one 256-wide panel at a time
-        for (int k = 0; k < (int)nP; ++k) {
-            const int64_t pk = panel_off(k, Np), mk = Np - (int64_t)TGP_PW * k;
-            const int64_t w0 = (int64_t)(2 * k) * TGP_TB * TGP_TB, w1 = w0 + TGP_TB * TGP_TB;
-            const int64_t r1 = pk + (int64_t)TGP_TB * TGP_PW;          // row 128 of the panel
-            const unsigned nr1 = (unsigned)((mk - TGP_TB) / TGP_TB), nr2 = (unsigned)((mk - TGP_PW) / TGP_TB);
-            bpotrf_kernel<<<ncn, 256, potrf_v2::POTRF_LDS_BYTES, st>>>(dA, dW, d, pk, w0, dinfo, k * TGP_PW);
-            bgemm_col_kernel<0, TGP_TB, true><<<dim3(nr1, ncn), 256, 0, st>>>(dA, dW, d, r1, w0, r1);
-            bgemm_col_kernel<1, TGP_PW, false><<<dim3(nr1, ncn), 256, 0, st>>>(dA, dW, d, r1, r1, r1 + TGP_TB);
-            bpotrf_kernel<<<ncn, 256, potrf_v2::POTRF_LDS_BYTES, st>>>(dA, dW, d, r1 + TGP_TB, w1, dinfo, k * TGP_PW + TGP_TB);
-            if (nr2 == 0) continue;
-            const int64_t r2 = pk + (int64_t)TGP_PW * TGP_PW + TGP_TB;   // row 256, column 128
-            bgemm_col_kernel<0, TGP_TB, true><<<dim3(nr2, ncn), 256, 0, st>>>(dA, dW, d, r2, w1, r2);
-            bsyrk_kernel<<<dim3((unsigned)(nr2 * (nr2 + 1) / 2), ncn), 256, 0, st>>>(dA, d, k, (int)nr2);
-        }
-        TGP_HIP(hipEventRecord(ctx->ev[2], st));
-
-        for (int j = 0; j < (int)nT; ++j)
-            bfwd_step_kernel<<<dim3((unsigned)(nT - j), ncn), 256, 0, st>>>(dA, dW, d, dy, dz, j);
-        bfinish_kernel<<<ncn, 256, 0, st>>>(dA, dz, dns, d, dout);
-        if (alpha) {
-            for (int j = (int)nT - 1; j >= 0; --j)
-                bbwd_step_kernel<<<dim3((unsigned)(j + 1), ncn), 256, 0, st>>>(dA, dW, d, dz, da, j);
-            bunpad_kernel<<<dim3((unsigned)((nmax + 255) / 256), ncn), 256, 0, st>>>(da, dns, nmax, Np, ra);
-        }
-        TGP_HIP(hipEventRecord(ctx->ev[3], st));
-        TGP_HIP(hipGetLastError());
-        TGP_HIP(hipMemcpyAsync(hinfo, dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipMemcpyAsync(hout, dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
-        if (alpha) TGP_HIP(hipMemcpyAsync(alpha + c0 * nmax, ra, (size_t)cn * nmax * 8, hipMemcpyDeviceToHost, st));
+        rc = batch_factor_chunk(ctx, d, bb, c0, cn, ks, ns, nmax, X, y, yerr, alpha != nullptr);
+        if (rc) return rc;
+        TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
+        if (alpha) TGP_HIP(hipMemcpyAsync(alpha + c0 * nmax, bb.ra, (size_t)cn * nmax * 8, hipMemcpyDeviceToHost, st));
         TGP_HIP(hipStreamSynchronize(st));
         float t0 = 0.f, t1 = 0.f, t2 = 0.f;
         TGP_HIP(hipEventElapsedTime(&t0, ctx->ev[0], ctx->ev[1]));
@@ -376,16 +552,8 @@ int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t
         ms_k += t0;
         ms_c += t1;
         ms_s += t2;
-        for (int64_t b = 0; b < cn; ++b) {
-            if (hinfo[b] < 0) {
-                ctx->err = "tgp_gp_solve_batch: a diagonal block of problem " + std::to_string((long long)(c0 + b)) +
-                           " reported an internal hand-off failure (info " + std::to_string(hinfo[b]) + ")";
-                return -2;
-            }
-            info[c0 + b] = hinfo[b];
-            logdet[c0 + b] = hout[2 * b];
-            if (ydota) ydota[c0 + b] = hout[2 * b + 1];
-        }
+        rc = batch_collect(ctx, fn, bb, c0, cn, logdet, ydota, info);
+        if (rc) return rc;
     }
     // only the slots this call fills: nothing of an earlier call on the context is left behind in the others
     for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
@@ -393,5 +561,130 @@ int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t
     ctx->timings[1] = ms_c;
     ctx->timings[2] = ms_s;
     ctx->timings[10] = alpha ? 2.0 : 1.0;
+    return 0;
+}
+
+// ---- S3f: the posterior variance or covariance of every problem of S2e from its factor, in the same call -------------------
+// Per chunk, after batch_factor_chunk: H_b into Bt_b (and Kss_b into C_b), the block substitution Bt_b <- H_b L_b^-T over the
+// 128-column blocks kb (trsm with W_kb, update of the blocks to its right), then amp_b - |Bt_b[i, :]|^2 or Kss_b - Bt_b Bt_b^T,
+// unpadded to the caller's layout on the device.
+#define TGP_POST_VAR_MMAX 65280       // the row grids of cov.hip (largest multiple of 256 <= 65 535)
+#define TGP_POST_COV_MMAX 4096
+
+int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                           const double *y, const double *yerr, const int64_t *ms, int64_t mmax, const double *Xs, int what,
+                           double *alpha, double *unc, double *logdet, double *ydota, int32_t *info) {
+    static const char *fn = "tgp_gp_posterior_batch";
+    if (!ctx) return -1;
+    if (!(ks && ns && X && y && ms && Xs && unc && logdet && info)) {
+        ctx->err = "tgp_gp_posterior_batch: ks, ns, X, y, ms, Xs, unc, logdet and info must not be NULL";
+        return -1;
+    }
+    if (what != 1 && what != 2) {
+        ctx->err = "tgp_gp_posterior_batch: what = " + std::to_string(what) + " is neither 1 (variance) nor 2 (covariance)";
+        return -1;
+    }
+    int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
+    if (rc) return rc;
+    const bool cov = what == 2;
+    const int64_t mlim = cov ? TGP_POST_COV_MMAX : TGP_POST_VAR_MMAX;
+    if (mmax < 1 || mmax > mlim) {
+        ctx->err = std::string(fn) + ": mmax must be in 1 .. " + std::to_string((long long)mlim) + (cov ? " for the covariance" : " for the variance");
+        return -1;
+    }
+    for (int b = 0; b < nb; ++b)
+        if (ms[b] < 1 || ms[b] > mmax) {
+            ctx->err = std::string(fn) + ": ms[" + std::to_string(b) + "] = " + std::to_string((long long)ms[b]) + " is not in 1 .. mmax = " +
+                       std::to_string((long long)mmax);
+            return -1;
+        }
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW, nT = Np / TGP_TB;
+    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
+    const PostDims q{(mmax + TGP_PW - 1) / TGP_PW * TGP_PW, mmax};
+    const int mt = (int)(q.Mp / TGP_TB);
+    // per problem: S2e's arrays, Bt, the query rows, ms, the result on the device (panels for the covariance) and unpadded
+    const size_t out_elems = cov ? (size_t)mmax * mmax : (size_t)mmax;
+    const size_t per = batch_bytes_per_problem(d, nmax) + rup((size_t)q.Mp * Np * 8) + rup((size_t)mmax * 16) + rup(8) +
+                       (cov ? rup((size_t)q.Mp * q.Mp * 8) : 0) + rup(out_elems * 8);
+    const size_t fixed = 8 * 256;
+    const int64_t C = batch_chunk(ctx, fn, nb, per, fixed, &rc);
+    if (rc) return rc;
+    rc = tgp_ensure_scratch(ctx, (size_t)C * per + fixed);
+    if (rc) return rc;
+    char *base = (char *)ctx->scratch;
+    size_t off = 0;
+    BatchBufs bb;
+    rc = batch_take(ctx, d, nmax, C, base, &off, &bb);
+    if (rc) return rc;
+    auto take = [&](size_t bytes) { void *p = base + off; off += rup(bytes); return p; };
+    double *dBt = (double *)take((size_t)C * q.Mp * Np * 8);
+    double *dXs = (double *)take((size_t)C * mmax * 16);
+    int64_t *dms = (int64_t *)take((size_t)C * 8);
+    double *dC = cov ? (double *)take((size_t)C * q.Mp * q.Mp * 8) : nullptr;
+    double *dU = (double *)take((size_t)C * out_elems * 8);
+
+    double ms_k = 0.0, ms_c = 0.0, ms_s = 0.0, ms_p = 0.0, ms_t = 0.0;
+    for (int64_t c0 = 0; c0 < nb; c0 += C) {
+        const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
+        const unsigned ncn = (unsigned)cn;
+        rc = batch_factor_chunk(ctx, d, bb, c0, cn, ks, ns, nmax, X, y, yerr, alpha != nullptr);
+        if (rc) return rc;
+        TGP_HIP(hipMemcpyAsync(dms, ms + c0, (size_t)cn * 8, hipMemcpyHostToDevice, st));
+        TGP_HIP(hipMemcpyAsync(dXs, Xs + c0 * mmax * 2, (size_t)cn * mmax * 16, hipMemcpyHostToDevice, st));
+        TGP_HIP(hipEventRecord(ctx->ev[4], st));
+        // H_b (and Kss_b), one launch per kernel evaluator present, as the K build
+        const unsigned gh = (unsigned)(q.Mp * (Np / 256)), gk = (unsigned)(q.Mp * (q.Mp / 256));
+        const int *cnt = bb.cnt, *start = bb.start;
+#define TGP_CROSS(KE, i)                                                                                                          \
+        if (cnt[i]) {                                                                                                                 \
+            bcross_kernel<KE><<<dim3(gh, cnt[i]), 256, 0, st>>>(bb.dkp, bb.dlist + start[i], bb.dns, dms, dXs, bb.dX, Np, q, 0, Np, dBt); \
+            if (cov) bcross_kernel<KE><<<dim3(gk, cnt[i]), 256, 0, st>>>(bb.dkp, bb.dlist + start[i], bb.dns, dms, dXs, bb.dX, Np, q, 1, q.Mp, dC); \
+        }
+        TGP_CROSS(KE_GAUSS, 0)
+        TGP_CROSS(KE_VK, 1)
+        TGP_CROSS(KE_AVK, 2)
+#undef TGP_CROSS
+        // Bt_b <- H_b L_b^-T
+        for (int kb = 0; kb < (int)nT; ++kb) {
+            btrsm_kernel<<<dim3((unsigned)mt, ncn), 256, 0, st>>>(dBt, bb.dW, bb.dns, dms, d, q, kb);
+            const int nc = (int)nT - kb - 1;
+            if (nc > 0) bupdate_kernel<<<dim3((unsigned)(mt * nc), ncn), 256, 0, st>>>(dBt, bb.dA, bb.dns, dms, d, q, kb, mt);
+        }
+        if (cov) {
+            bsyrk_cov_kernel<<<dim3((unsigned)(mt * mt), ncn), 256, 0, st>>>(dC, dBt, dms, Np, q, mt);
+            bunpad_cov_kernel<<<dim3((unsigned)(mmax * ((mmax + 255) / 256)), ncn), 256, 0, st>>>(dC, dms, q, dU);
+        } else {
+            bvar_rows_kernel<<<dim3((unsigned)((mmax + 3) / 4), ncn), 256, 0, st>>>(dBt, bb.dkp, dms, Np, q, dU);
+        }
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipEventRecord(ctx->ev[5], st));
+        TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
+        if (alpha) TGP_HIP(hipMemcpyAsync(alpha + c0 * nmax, bb.ra, (size_t)cn * nmax * 8, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipMemcpyAsync(unc + (size_t)c0 * out_elems, dU, (size_t)cn * out_elems * 8, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipEventRecord(ctx->ev[6], st));
+        TGP_HIP(hipStreamSynchronize(st));
+        float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        TGP_HIP(hipEventElapsedTime(&t[0], ctx->ev[0], ctx->ev[1]));
+        TGP_HIP(hipEventElapsedTime(&t[1], ctx->ev[1], ctx->ev[2]));
+        TGP_HIP(hipEventElapsedTime(&t[2], ctx->ev[2], ctx->ev[3]));
+        TGP_HIP(hipEventElapsedTime(&t[3], ctx->ev[4], ctx->ev[5]));
+        TGP_HIP(hipEventElapsedTime(&t[4], ctx->ev[5], ctx->ev[6]));
+        ms_k += t[0];
+        ms_c += t[1];
+        ms_s += t[2];
+        ms_p += t[3];
+        ms_t += t[4];
+        rc = batch_collect(ctx, fn, bb, c0, cn, logdet, ydota, info);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
+    ctx->timings[0] = ms_k;
+    ctx->timings[1] = ms_c;
+    ctx->timings[2] = ms_s;
+    ctx->timings[3] = ms_p;
+    ctx->timings[9] = ms_t;
     return 0;
 }

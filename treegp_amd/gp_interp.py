@@ -402,38 +402,97 @@ class GPInterpolation(object):
         raise NotImplementedError("plotting (treegp/gp_interp.py:293-377) is outside the GPU hot path")
 
 
-def predict_many(gps, Xs):
+def predict_many(gps, Xs, return_cov=False, return_var=False):
     """``[gp.predict(X) for gp, X in zip(gps, Xs)]`` with the solves of many small GPs in one batched factorisation (the
     reference's regime: one GP per PSF parameter, exposure or chip, README.rst:28).  ``gps``: initialised GPInterpolation
     objects; ``Xs``: their query points.  The objects whose kernel ``kernel_to_spec`` describes, that are not on the
     multi-GPU route, hold at most 4096 points and have no cached solution get their alpha from one batched solve
     (ops.gp_solve_batch); it is cached in ``gp._alpha`` as ``predict`` caches it, so that a later ``gp.predict`` reuses
     it.  Every object then predicts through its own ``predict``: the others solve there as usual.  A failed
-    factorisation raises numpy.linalg.LinAlgError naming the object's index (nothing is cached then)."""
+    factorisation raises numpy.linalg.LinAlgError naming the object's index (nothing is cached then).
+
+    ``return_cov=True`` / ``return_var=True`` return a list of ``(y, cov)`` / ``(y, var)`` with what each object's
+    ``gp.predict(X, return_cov=True)`` / ``return_var=True`` gives: the posterior of the objects above (a cached solution
+    does not exclude them here) with at most 4096 (covariance) or 65 280 (variance) query points and no kept factor of the
+    same data comes from one batched factorisation and substitution (ops.gp_posterior_batch); a cached alpha is kept, an
+    object without one caches the batch's, and no kept factor is left behind.  The mean is each object's own ``predict(X)``
+    from its cached alpha.  Every other object goes through its own ``predict``.  At most one flag may be True."""
+    if return_cov and return_var:
+        raise ValueError("at most one of return_cov and return_var may be True")
     gps, Xs = list(gps), list(Xs)
     if len(gps) != len(Xs):
         raise ValueError("predict_many: %d GPs but %d arrays of query points" % (len(gps), len(Xs)))
+    if return_cov or return_var:
+        return _predict_many_posterior(gps, Xs, "cov" if return_cov else "var")
     picked, specs = [], []
     for i, gp in enumerate(gps):
-        if gp._alpha is not None or gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX:
+        if gp._alpha is not None:
             continue
-        try:
-            spec = kernel_to_spec(gp.kernel)
-        except NotImplementedError:
+        spec = _batch_spec(gp)
+        if spec is None:
             continue
-        with gp._scope():
-            if ops._dist_engine(len(gp._X), None) is not None:
-                continue
         picked.append(i)
         specs.append(spec)
     if picked:
         alphas, _, _, info = ops.gp_solve_batch(specs, [gps[i]._X for i in picked], [gps[i]._residual() for i in picked],
                                                 [gps[i]._y_err for i in picked])
-        for j, i in enumerate(picked):
-            if info[j] > 0:
-                raise np.linalg.LinAlgError("predict_many: GP %d: %d-th leading minor of the array is not positive definite"
-                                            % (i, info[j]))
+        _raise_failed(picked, info)
         for j, i in enumerate(picked):
             gps[i]._alpha = alphas[j]
             gps[i]._set_factor(None, None)        # what predict's own solve leaves: no kept factor
     return [gp.predict(X) for gp, X in zip(gps, Xs)]
+
+
+def _batch_spec(gp):
+    """the device kernel of an object the batched routes may take (kernel_to_spec describes it, not on the multi-GPU
+    route, at most 4096 points), else None"""
+    if gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX:
+        return None
+    try:
+        spec = kernel_to_spec(gp.kernel)
+    except NotImplementedError:
+        return None
+    with gp._scope():
+        if ops._dist_engine(len(gp._X), None) is not None:
+            return None
+    return spec
+
+
+def _raise_failed(picked, info):
+    for j, i in enumerate(picked):
+        if info[j] > 0:
+            raise np.linalg.LinAlgError("predict_many: GP %d: %d-th leading minor of the array is not positive definite"
+                                        % (i, info[j]))
+
+
+def _predict_many_posterior(gps, Xs, what):
+    picked, specs = [], []
+    for i, gp in enumerate(gps):
+        m = len(Xs[i])
+        if m < 1 or m > ops.POSTERIOR_MMAX[what]:
+            continue
+        spec = _batch_spec(gp)
+        if spec is None:
+            continue
+        if gp._factor is not None and gp._factor_key == gp._factor_fingerprint(spec, gp._X, gp._y_err):
+            continue                              # its own predict reuses the kept factor: no factorisation to save
+        picked.append(i)
+        specs.append(spec)
+    uncs = {}
+    if picked:
+        alphas, unc, _, _, info = ops.gp_posterior_batch(specs, [gps[i]._X for i in picked],
+                                                         [gps[i]._residual() for i in picked],
+                                                         [gps[i]._y_err for i in picked], [Xs[i] for i in picked], what=what)
+        _raise_failed(picked, info)
+        for j, i in enumerate(picked):
+            if gps[i]._alpha is None:
+                gps[i]._alpha = alphas[j]         # a cached alpha stays, as in _ensure_solution
+            gps[i]._set_factor(None, None)
+            uncs[i] = unc[j]
+    out = []
+    for i, (gp, X) in enumerate(zip(gps, Xs)):
+        if i in uncs:
+            out.append((gp.predict(X), uncs[i]))
+        else:
+            out.append(gp.predict(X, return_cov=what == "cov", return_var=what == "var"))
+    return out

@@ -179,6 +179,58 @@ def gp_solve_batch(specs, Xs, ys, y_errs=None, want_alpha=True, ctx=None):
     return alphas, logdet, chi2, info.astype(np.int64)
 
 
+POSTERIOR_MMAX = {"var": 65280, "cov": 4096}    # tgp_gp_posterior_batch: query points per problem (the row grids of S3b / S3c)
+
+
+def gp_posterior_batch(specs, Xs, ys, y_errs, Xqs, what="var", want_alpha=True, ctx=None):
+    """gp_solve_batch plus, from each problem's factor in the same call, the posterior at its query points Xqs[b] (m_b, 1 or 2)
+    (tgp_gp_posterior_batch): what="var" gives the variance (m_b,) as gp_predict_var, what="cov" the covariance (m_b, m_b) as
+    gp_predict_cov.  Returns (alphas or None, uncs, logdets, chi2, info); alphas, logdets, chi2 and info are bit for bit what
+    gp_solve_batch returns for the same batch, and a problem with info[b] > 0 has meaningless outputs."""
+    if what not in POSTERIOR_MMAX:
+        raise ValueError("gp_posterior_batch: what must be 'var' or 'cov', got %r" % (what,))
+    specs = list(specs)
+    ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("gp_posterior_batch: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("gp_posterior_batch: problems of order up to %d, got %d (use gp_solve)" % (BATCH_NMAX, nmax))
+    Xqs = list(Xqs)
+    if len(Xqs) != nb:
+        raise ValueError("gp_posterior_batch: %d problems but %d arrays of query points" % (nb, len(Xqs)))
+    Xq2 = [as_xy(X) for X in Xqs]
+    ms = np.array([X.shape[0] for X in Xq2], dtype=np.int64)
+    if np.any(ms < 1):
+        raise ValueError("gp_posterior_batch: every problem needs at least one query point")
+    mmax = int(ms.max())
+    if mmax > POSTERIOR_MMAX[what]:
+        raise ValueError("gp_posterior_batch: what=%r takes up to %d query points per problem, got %d"
+                         % (what, POSTERIOR_MMAX[what], mmax))
+    Xqb = np.zeros((nb, mmax, 2))
+    for b in range(nb):
+        Xqb[b, :ms[b]] = Xq2[b]
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    alpha = np.empty((nb, nmax)) if want_alpha else None
+    unc = np.empty((nb, mmax, mmax) if what == "cov" else (nb, mmax))
+    logdet = np.empty(nb)
+    chi2 = np.empty(nb)
+    info = np.zeros(nb, dtype=np.int32)
+    rc = lib.tgp_gp_posterior_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(ms), mmax,
+                                    ptr(Xqb), 2 if what == "cov" else 1, ptr(alpha), ptr(unc), ptr(logdet), ptr(chi2), ptr(info))
+    check(ctx, rc, "tgp_gp_posterior_batch")
+    alphas = [alpha[b, :int(ns[b])].copy() for b in range(nb)] if want_alpha else None
+    # a problem with mmax points gets a view of the batch's array (no second copy of up to 128 MiB per covariance), the
+    # others a compact copy of their block
+    if what == "cov":
+        uncs = [unc[b] if ms[b] == mmax else unc[b, :ms[b], :ms[b]].copy() for b in range(nb)]
+    else:
+        uncs = [unc[b] if ms[b] == mmax else unc[b, :ms[b]].copy() for b in range(nb)]
+    return alphas, uncs, logdet, chi2, info.astype(np.int64)
+
+
 def gp_solve_dense(K, y, y_err=None, keep=False, want_alpha=True, ctx=None):
     """gp_solve for a kernel matrix evaluated by the caller (any scikit-learn kernel tree): K (n, n), lower triangle
     read; y_err^2 is added to the diagonal on the device (tgp_gp_solve_dense)."""
