@@ -48,14 +48,22 @@ __global__ __launch_bounds__(256) void predict_partial_kernel(KParams p, const d
 // ---- Gaussian fast path ---------------------------------------------------------------------------
 // exp(-0.5 d^T invLam d) with invLam = L L^T is 2^-(|u|^2) for u = sqrt(0.5 log2 e) L^T d.  Coordinates
 // are transformed once per call (O(n + m)), which leaves 2 sub + 1 mul + 1 fma for the exponent, and
-// 2^-s needs no range checks for s >= 0: 22 fp64 instructions per pair instead of 32.  The rounding of
-// the exponent differs from the reference's a dx^2 + 2 b dx dy + c dy^2 by ~1e-16 |q| relative
-// (parity tests: 1e-10 on predicted values).  The amplitude is applied in the reduction.
-__global__ __launch_bounds__(256) void predict_transform_kernel(const double *__restrict__ X, int64_t n, double t00,
+// 2^-s needs no range checks for s >= 0: 22 fp64 instructions per pair instead of 32.  The amplitude is
+// applied in the reduction.
+// Accuracy: the transformed coordinates are rounded before the difference of a pair is taken, so the
+// exponent s = q/2 of a pair carries roundings relative to sqrt(S), S = the largest exponent between
+// any two points of the call (the data's diameter), not to sqrt(s):
+//     |value - amp exp(-q/2)| <= (8 + 16 sqrt(s S)) 2^-53 amp exp(-q/2) + 2 * 2^-1074
+// (tests/test_gpu_kernel_values.py checks every pair against mpmath with this bound).  The origin of
+// the transform is the first training point, subtracted BEFORE the transform (exact for data whose
+// spread is small against its offset, Sterbenz), so S is a property of the spread and the result is
+// translation invariant: without it coordinates at an offset of 2^20 lost seven digits.
+__global__ __launch_bounds__(256) void predict_transform_kernel(const double *__restrict__ X, int64_t n,
+                                                                const double *__restrict__ origin, double t00,
                                                                 double t10, double t11, double *__restrict__ U) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const double x = X[2 * i], y = X[2 * i + 1];
+    const double x = X[2 * i] - origin[0], y = X[2 * i + 1] - origin[1];
     U[2 * i] = t00 * x + t10 * y;
     U[2 * i + 1] = t11 * y;
 }
@@ -281,8 +289,8 @@ int launch_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t
         const double t00 = sc * l00, t10 = sc * l10, t11 = sc * sqrt(d11);
         double *U = (double *)((char *)ctx->scratch + rup((size_t)nsplit * m * 8));
         double *Us = (double *)((char *)U + rup(2 * n * 8));
-        predict_transform_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_X, n, t00, t10, t11, U);
-        predict_transform_kernel<<<(unsigned)((m + 255) / 256), 256, 0, ctx->stream>>>(d_Xs, m, t00, t10, t11, Us);
+        predict_transform_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_X, n, d_X, t00, t10, t11, U);
+        predict_transform_kernel<<<(unsigned)((m + 255) / 256), 256, 0, ctx->stream>>>(d_Xs, m, d_X, t00, t10, t11, Us);
         if (exp_tab == 32) predict_gauss_tab_kernel<32><<<grid, block, 0, ctx->stream>>>(U, n, d_alpha, Us, m, partial, chunk);
         else if (exp_tab == 64) predict_gauss_tab_kernel<64><<<grid, block, 0, ctx->stream>>>(U, n, d_alpha, Us, m, partial, chunk);
         else if (exp_tab == 256) predict_gauss_tab_kernel<256><<<grid, block, 0, ctx->stream>>>(U, n, d_alpha, Us, m, partial, chunk);
