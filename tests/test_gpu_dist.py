@@ -105,7 +105,9 @@ def test_hand_offs_by_stream_wait_value_pass_their_trial_here():
     assert "mode 2" in r.stdout, r.stdout + r.stderr
 
 
-def _run_virtual_ranks(G, n):
+def _run_virtual_ranks(G, n, capture=None):
+    """`capture(rank, gp)`: called on every rank's thread once its step is done and the device is idle (test_gpu_dist_blocks.py
+    clones the rank's share of the factor there)"""
     import torch
     from treegp_amd import _lib, ops
     from treegp_amd.dist import DistributedGP
@@ -127,6 +129,8 @@ def _run_virtual_ranks(G, n):
             full = gp.gather_predictions()
             torch.cuda.synchronize()
             results[rank] = (alpha.cpu().numpy()[:n], float(gp.logdet[0]), full.cpu().numpy())
+            if capture is not None:
+                capture(rank, gp)
         except BaseException as e:            # noqa: BLE001 - surface any failure of a virtual rank
             errors.append(e)
             try:

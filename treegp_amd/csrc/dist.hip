@@ -300,7 +300,8 @@ int tgp_dd_bwd_partial(tgp_ctx *ctx, const double *d_Aloc, const int64_t *h_loff
     const int64_t below = dist_panel_blocks(kb + 1, nB, g, G);
     const int64_t skip = (dist_owner(kb, G) == g) ? TGP_PW : 0;
     const int64_t lb0 = (below > 0) ? dist_first_round(kb + 1, g, G) : 0;
-    return launch_gemv_t_rows(ctx, d_Aloc + h_loff[kb] + skip * TGP_PW, below * TGP_PW, d_aloc + lb0 * TGP_PW, d_s);
+    return launch_gemv_t_rows(ctx, d_Aloc + h_loff[kb] + skip * TGP_PW, below * TGP_PW, d_aloc + lb0 * TGP_PW, d_s,
+                              dist_panel_blocks(0, nB, g, G) * TGP_PW);
 }
 // backward sweep, block kb (owner): a_k (256) <- L_kk^-T (a_k - s)   (d_s may be NULL)
 int tgp_dd_bwd_diag(tgp_ctx *ctx, const double *d_Aloc, const int64_t *h_loff, int kb, const double *d_W, double *d_ak,

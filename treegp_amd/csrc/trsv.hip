@@ -193,24 +193,6 @@ __global__ void pad_copy_kernel(const double *__restrict__ y, int64_t n, int64_t
     if (i < Np) b[i] = i < n ? y[i] : 0.0;
 }
 
-// out[c] += sign * sum_r L[r][c] a[r] over `rows` rows of a 128-column block (ld 256); partial sums
-// per workgroup are combined with global fp64 atomics (out must be initialised by the caller)
-__global__ __launch_bounds__(256) void gemv_t_acc_kernel(const double *__restrict__ L, int64_t rows,
-                                                         const double *__restrict__ a, double *out, double sign) {
-    __shared__ double part[256];
-    const int tid = threadIdx.x, c = tid & 127, h = tid >> 7;
-    const int64_t r0 = (int64_t)blockIdx.x * 128;
-    const int64_t r1 = (r0 + 128 < rows) ? r0 + 128 : rows;
-    double s = 0.0;
-    for (int64_t r = r0 + h; r < r1; r += 2) s += L[r * TGP_PW + c] * a[r];
-    part[tid] = s;
-    __syncthreads();
-    if (tid < 128) {
-        const double v = sign * (part[tid] + part[tid + 128]);
-        __hip_atomic_fetch_add(out + tid, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // multi-GPU log-determinant share: sum over the diagonal blocks this rank owns
 __global__ __launch_bounds__(1024) void logdet_dist_kernel(const double *__restrict__ Aloc,
                                                            const int64_t *__restrict__ loff, int64_t nB, int64_t n,
@@ -298,6 +280,13 @@ __global__ __launch_bounds__(256) void bwd_partial_kernel(const double *__restri
     }
     for (; r < r1; ++r) s0 += Lrows[r * TGP_PW + tid] * a[r];
     partial[(int64_t)blockIdx.x * TGP_PW + tid] = (s0 + s1) + (s2 + s3);
+}
+
+// s (256) = sum of npart partial vectors, in order
+__global__ __launch_bounds__(256) void sum_partials256_kernel(const double *__restrict__ partial, int npart, double *__restrict__ s) {
+    double acc = 0.0;
+    for (int k = 0; k < npart; ++k) acc += partial[(int64_t)k * TGP_PW + threadIdx.x];
+    s[threadIdx.x] = acc;
 }
 
 // y (256) <- L_pp^-T (y - sum of npart partial vectors):  t1 = W1^T y1; y0 -= L10^T t1; t0 = W0^T y0
@@ -618,14 +607,24 @@ int launch_fwd_update_rows(tgp_ctx *ctx, const double *Lrows, int64_t rows, cons
     TGP_HIP(hipGetLastError());
     return 0;
 }
-// s (256) = sum_r L[r, 0:256]^T a[r]   (s zeroed here)
-int launch_gemv_t_rows(tgp_ctx *ctx, const double *Lrows, int64_t rows, const double *a, double *s) {
+// s (256) = sum_r L[r, 0:256]^T a[r] over `rows` rows (ld 256): one partial vector per 128 rows, added up in a fixed order -- the
+// same bits on every run (fp64 atomics used to combine them in the order the workgroups happened to finish, and alpha then
+// differed from run to run on the same factor).  `max_rows`: the most rows any call on
+// this factor passes (sizes the partials once instead of growing them step by step through the sweep)
+int launch_gemv_t_rows(tgp_ctx *ctx, const double *Lrows, int64_t rows, const double *a, double *s, int64_t max_rows) {
     hipStream_t st = ctx->stream;
-    TGP_HIP(hipMemsetAsync(s, 0, TGP_PW * sizeof(double), st));
-    if (rows <= 0) return 0;
-    const unsigned g = (unsigned)((rows + 127) / 128);
-    gemv_t_acc_kernel<<<g, 256, 0, st>>>(Lrows, rows, a, s, 1.0);
-    gemv_t_acc_kernel<<<g, 256, 0, st>>>(Lrows + TGP_TB, rows, a, s + TGP_TB, 1.0);
+    if (rows <= 0) {
+        TGP_HIP(hipMemsetAsync(s, 0, TGP_PW * sizeof(double), st));
+        return 0;
+    }
+    const int chunk = 128;
+    if (max_rows < rows) max_rows = rows;
+    int rc = tgp_ensure_scratch2(ctx, (size_t)((max_rows + chunk - 1) / chunk) * TGP_PW * sizeof(double));
+    if (rc) return rc;
+    double *partial = (double *)ctx->scratch2;
+    const int npart = (int)((rows + chunk - 1) / chunk);
+    bwd_partial_kernel<<<npart, 256, 0, st>>>(Lrows, rows, chunk, a, partial);
+    sum_partials256_kernel<<<1, 256, 0, st>>>(partial, npart, s);
     TGP_HIP(hipGetLastError());
     return 0;
 }
