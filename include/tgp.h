@@ -7,6 +7,7 @@
  *   S1  kernel.__call__(X[,Y])           treegp/kernels.py:114-126, 249-276, 355-381
  *   S2  cholesky + cho_solve (+ logdet)  treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33
  *   S2e many small S2 at once           treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33, 43-62, README.rst:28
+ *   S2f many small S2 + S2d at once     treegp/log_likelihood.py:43-62 for the problems of S2e (one evaluation of many fits)
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
@@ -144,6 +145,23 @@ int tgp_factor_solve(tgp_ctx *ctx, tgp_factor *f, const double *B, int nrhs, dou
  * without alpha); every other slot 0.                                                                                  */
 int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
                        const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info);
+
+/* ---- S2f: S2 and the likelihood gradient S2d for the nb problems of S2e, in the same call ------------------------------------
+ * A maximum-likelihood fit (treegp/log_likelihood.py:43-62) evaluates the likelihood 37-82 times; with one GP per PSF
+ * parameter, exposure or chip (README.rst:28) many such fits run side by side, and one call here is one evaluation of all of
+ * them.  The batch of S2e is factorised and solved as tgp_gp_solve_batch does it and, in the same chunk, each problem's factor
+ * and alpha give
+ *   grad[b][0..3] = 1/2 sum_ij (alpha_i alpha_j - [K^-1]_ij) dK_ij/dp   for p = log amp, a, b, c
+ * in the convention and element order of tgp_gp_loglik_grad.  ks, ns, nmax, X, y, yerr, logdet, ydota and info as
+ * tgp_gp_solve_batch; logdet and ydota are bit for bit what it returns; a problem with info[b] > 0 has meaningless outputs and
+ * the others are unaffected, bit for bit.  A problem's bits depend neither on its companions, nor on its place in the batch,
+ * nor on the chunking (TGP_BATCH_CHUNK, as S2e; the chunk also holds L^-T and K^-1, Np x Np each, per problem).
+ * Gaussian kernels only (TGP_RBF, TGP_ARBF): a von Karman kind anywhere in ks returns -1 with a message naming the entry.
+ * Returns 0 when every problem was attempted; -1 for the argument errors of S2e; -2 for HIP errors.  Timings [0] K build,
+ * [1] Cholesky, [2] sweeps and logdet, [3] inverse and reduction, summed over the chunks; every other slot 0.              */
+int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+                            const double *X, const double *y, const double *yerr,
+                            double *logdet, double *ydota, double *grad, int32_t *info);
 
 /* ---- S3: ys[j] = sum_i amp k(Xs_j, X_i) alpha_i, HT never materialised -------------------*/
 int tgp_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n,

@@ -12,6 +12,7 @@
 //   logdet, chi2   one workgroup per problem
 // Plain launches on the context's one stream, no in-kernel waits, no atomics in any sum.  Tile forms and summation depths
 // depend only on the panel index and Np, so a problem's bits do not depend on its companions, its place or the chunking.
+// The posterior (S3f) and the likelihood gradient (S2f) of every problem follow from its factor in the same chunk, further down.
 #define TGP_POTRF_BODY_ONLY
 #include "tgp_internal.h"
 #include "kernel_eval.h"
@@ -315,6 +316,126 @@ __global__ __launch_bounds__(256) void bunpad_cov_kernel(const double *__restric
     const int64_t m = ms[b];
     out[((int64_t)b * q.mmax + i) * q.mmax + j] =
         (i < m && j < m) ? C[(int64_t)b * q.Mp * q.Mp + (j >> 8) * q.Mp * TGP_PW + i * TGP_PW + (j & 255)] : 0.0;
+}
+
+// ---- likelihood gradient of every problem (seam S2f): S2d of cov.hip with the problem index on the grid ------------------------
+// Problem b's Bt_b = L_b^-T and C_b = -K_b^-1 are Np x Np in the 256-wide panel layout of cov.hip (Bt_b at b * Np * Np, panel p
+// at + p * Np * 256).  Bt_b starts as the identity and is upper triangular: row tile ti is zero left of column block ti, so the
+// substitution's step kb covers the row tiles ti <= kb only (btrsm_kernel / bupdate_kernel above with kb + 1 row tiles, ms = ns)
+// and C_b is formed over the lower tile pairs, each summed from panel ti / 2 on.  Nothing left of that is ever read, so nothing
+// there is initialised.  Row tiles at or beyond n_b are skipped by the problem's own n_b; column blocks beyond it hold exact
+// zeros in the rows below n_b.  Tile forms and summation depths depend on the tile indices and Np only, and the trailing
+// zeros of a larger Np add nothing: a problem's bits do not depend on its companions, its place, the chunking or nmax.
+struct GradDims {
+    int64_t nrb;   // 64-row blocks of Np
+    int64_t nP;    // 256-column panels of Np
+};
+
+// Bt_b <- identity, C_b <- 0 where they are read: row tile ti = blockIdx.x / nP below n_b, panel p = blockIdx.x % nP of Bt_b from
+// ti / 2 on, of C_b up to ti / 2
+__global__ __launch_bounds__(256) void bgrad_init_kernel(double *__restrict__ Bt, double *__restrict__ C, const int64_t *__restrict__ ns,
+                                                         int64_t Np, int nP) {
+    const int b = blockIdx.y;
+    const int64_t ti = blockIdx.x / nP, p = blockIdx.x % nP;
+    if (ti * TGP_TB >= ns[b]) return;
+    const int64_t base = (int64_t)b * Np * Np + p * Np * TGP_PW + ti * TGP_TB * TGP_PW;
+    const int r0 = threadIdx.x >> 7, c = 2 * (threadIdx.x & 127);
+    if (p >= (ti >> 1)) {
+        for (int r = r0; r < TGP_TB; r += 2) {
+            const int64_t i = ti * TGP_TB + r, j = p * TGP_PW + c;
+            double2 v = {j == i ? 1.0 : 0.0, j + 1 == i ? 1.0 : 0.0};
+            *reinterpret_cast<double2 *>(Bt + base + (int64_t)r * TGP_PW + c) = v;
+        }
+    }
+    if (p <= (ti >> 1)) {
+        const double2 z = {0.0, 0.0};
+        for (int r = r0; r < TGP_TB; r += 2) *reinterpret_cast<double2 *>(C + base + (int64_t)r * TGP_PW + c) = z;
+    }
+}
+
+// lower tile pairs (ti >= tj), linear in blockIdx.x: C_b(ti, tj) = -sum_{p >= ti / 2} Bt_b[ti][p] Bt_b[tj][p]^T (kinv_syrk_kernel)
+__global__ __launch_bounds__(256, 2) void bkinv_syrk_kernel(double *C, const double *Bt, const int64_t *__restrict__ ns, int64_t Np, int nP) {
+    const int b = blockIdx.y;
+    const int64_t t = blockIdx.x;
+    int64_t ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (ti * (ti + 1) / 2 > t) --ti;
+    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    const int64_t tj = t - ti * (ti + 1) / 2;
+    if (ti * TGP_TB >= ns[b]) return;
+    const int64_t p0 = ti >> 1;
+    const double *Btb = Bt + (int64_t)b * Np * Np + p0 * Np * TGP_PW;
+    double *c = C + (int64_t)b * Np * Np + (tj >> 1) * Np * TGP_PW + ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
+    gemm_tile_dtv<4, TGP_PW, 0>(Btb + ti * TGP_TB * TGP_PW, Btb + tj * TGP_TB * TGP_PW, c, nullptr, nullptr, nP - (int)p0, Np * TGP_PW,
+                                Np * TGP_PW);
+}
+
+// loglik_grad_kernel's body for problem b = blockIdx.y: 64 rows (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the
+// lower triangle below n_b, four partial sums per workgroup at partial[(b * nrb * nP + blockIdx.x) * 4]
+__global__ __launch_bounds__(256) void bloglik_grad_kernel(const KParams *__restrict__ kp, const int64_t *__restrict__ ns,
+                                                           const double *__restrict__ X, const double *__restrict__ alpha,
+                                                           const double *__restrict__ C, int64_t Np, GradDims g,
+                                                           double *__restrict__ partial) {
+    __shared__ double red[4][4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int64_t n = ns[b];
+    const int64_t pj = blockIdx.x % g.nP, i0 = (int64_t)(blockIdx.x / g.nP) * 64;
+    if (i0 >= n || pj * TGP_PW >= n) return;                      // whole workgroups leave together; never summed
+    const KParams p = kp[b];
+    const double *Xb = X + (int64_t)b * 2 * Np, *ab = alpha + (int64_t)b * Np;
+    const int64_t j = pj * TGP_PW + tid;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (pj * TGP_PW <= i0 + 63 && j < n) {
+        const double xj = Xb[2 * j], yj = Xb[2 * j + 1], aj = ab[j];
+        const double *col = C + (int64_t)b * Np * Np + pj * Np * TGP_PW + tid;
+        for (int r = 0; r < 64; ++r) {
+            const int64_t i = i0 + r;
+            if (i >= n) break;
+            if (j > i) continue;
+            const double m = ab[i] * aj + col[i * TGP_PW];          // alpha_i alpha_j - [K^-1]_ij   (C holds -K^-1)
+            if (i == j) {
+                acc[0] += 0.5 * m * p.amp;                          // the pair (i, i) counts once, d K_ii / d log amp = amp
+            } else {
+                const double dx = Xb[2 * i] - xj, dy = Xb[2 * i + 1] - yj;
+                const double e = p.amp * exp(-0.5 * quad_form(p, dx, dy)) * m;
+                acc[0] += e;
+                acc[1] -= 0.5 * e * dx * dx;
+                acc[2] -= e * dx * dy;
+                acc[3] -= 0.5 * e * dy * dy;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double v = acc[q];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+    }
+    __syncthreads();
+    if (tid < 4) partial[(((int64_t)b * g.nrb * g.nP) + blockIdx.x) * 4 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// one workgroup per problem: its partial sums (row blocks below n_b x panels below n_b, that order) in a fixed order that depends
+// on n_b alone
+__global__ __launch_bounds__(256) void bloglik_grad_reduce_kernel(const double *__restrict__ partial, const int64_t *__restrict__ ns,
+                                                                  GradDims g, double *__restrict__ out) {
+    __shared__ double red[256][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t n = ns[b];
+    const int64_t nrb = (n + 63) / 64, nP = (n + TGP_PW - 1) / TGP_PW;
+    const double *pb = partial + (int64_t)b * g.nrb * g.nP * 4;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t q = tid; q < nrb * nP; q += 256) {
+        const int64_t rb = q / nP, p = q % nP;
+        for (int s = 0; s < 4; ++s) acc[s] += pb[(rb * g.nP + p) * 4 + s];
+    }
+    for (int s = 0; s < 4; ++s) red[tid][s] = acc[s];
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step)
+            for (int s = 0; s < 4; ++s) red[tid][s] += red[tid + step][s];
+        __syncthreads();
+    }
+    if (tid < 4) out[(int64_t)b * 4 + tid] = red[0][tid];
 }
 
 inline size_t rup(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -686,5 +807,98 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
     ctx->timings[2] = ms_s;
     ctx->timings[3] = ms_p;
     ctx->timings[9] = ms_t;
+    return 0;
+}
+
+// ---- S2f: the likelihood gradient of every problem of S2e from its factor and alpha, in the same call ---------------------------
+// Per chunk, after batch_factor_chunk with both sweeps: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row
+// tiles, C_b = -Bt_b Bt_b^T over the lower tile pairs, the reduction against dK/dp and one fixed-order sum per problem.
+// per problem beside S2e's arrays: Bt and C (Np x Np each), the reduction's partial sums, the four results
+static size_t grad_bytes_per_problem(const BatchDims &d, int64_t nmax) {
+    const size_t nparts = (size_t)(d.Np / 64) * (size_t)(d.Np / TGP_PW);
+    return batch_bytes_per_problem(d, nmax) + 2 * rup((size_t)d.Np * d.Np * 8) + rup(nparts * 32) + rup(32);
+}
+
+int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                            const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
+    static const char *fn = "tgp_gp_solve_grad_batch";
+    if (!ctx) return -1;
+    if (!(ks && ns && X && y && logdet && grad && info)) {
+        ctx->err = "tgp_gp_solve_grad_batch: ks, ns, X, y, logdet, grad and info must not be NULL";
+        return -1;
+    }
+    int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
+    if (rc) return rc;
+    for (int b = 0; b < nb; ++b)
+        if (kind_to_ke(ks[b].kind) != KE_GAUSS) {
+            ctx->err = std::string(fn) + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks[b].kind) +
+                       ": analytic derivatives exist for the Gaussian kernels only (RBF, AnisotropicRBF), as in the reference "
+                       "(treegp/kernels.py:128-150)";
+            return -1;
+        }
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW, nT = Np / TGP_TB;
+    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
+    const PostDims q{Np, nmax};                                   // Bt_b is square: the "query rows" are the problem's own
+    const GradDims g{Np / 64, nP};
+    const size_t per = grad_bytes_per_problem(d, nmax);
+    const size_t fixed = 8 * 256;
+    const int64_t C = batch_chunk(ctx, fn, nb, per, fixed, &rc);
+    if (rc) return rc;
+    rc = tgp_ensure_scratch(ctx, (size_t)C * per + fixed);
+    if (rc) return rc;
+    char *base = (char *)ctx->scratch;
+    size_t off = 0;
+    BatchBufs bb;
+    rc = batch_take(ctx, d, nmax, C, base, &off, &bb);
+    if (rc) return rc;
+    auto take = [&](size_t bytes) { void *p = base + off; off += rup(bytes); return p; };
+    double *dBt = (double *)take((size_t)C * Np * Np * 8);
+    double *dC = (double *)take((size_t)C * Np * Np * 8);
+    double *dpart = (double *)take((size_t)C * g.nrb * g.nP * 32);
+    double *dgrad = (double *)take((size_t)C * 32);
+
+    double ms_k = 0.0, ms_c = 0.0, ms_s = 0.0, ms_g = 0.0;
+    for (int64_t c0 = 0; c0 < nb; c0 += C) {
+        const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
+        const unsigned ncn = (unsigned)cn;
+        rc = batch_factor_chunk(ctx, d, bb, c0, cn, ks, ns, nmax, X, y, yerr, true);
+        if (rc) return rc;
+        TGP_HIP(hipEventRecord(ctx->ev[4], st));
+        bgrad_init_kernel<<<dim3((unsigned)(nT * nP), ncn), 256, 0, st>>>(dBt, dC, bb.dns, Np, (int)nP);
+        // Bt_b <- L_b^-T: at step kb only the row tiles ti <= kb hold anything
+        for (int kb = 0; kb < (int)nT; ++kb) {
+            const int live = kb + 1;
+            btrsm_kernel<<<dim3((unsigned)live, ncn), 256, 0, st>>>(dBt, bb.dW, bb.dns, bb.dns, d, q, kb);
+            const int nc = (int)nT - kb - 1;
+            if (nc > 0) bupdate_kernel<<<dim3((unsigned)(live * nc), ncn), 256, 0, st>>>(dBt, bb.dA, bb.dns, bb.dns, d, q, kb, live);
+        }
+        bkinv_syrk_kernel<<<dim3((unsigned)(nT * (nT + 1) / 2), ncn), 256, 0, st>>>(dC, dBt, bb.dns, Np, (int)nP);
+        bloglik_grad_kernel<<<dim3((unsigned)(g.nrb * g.nP), ncn), 256, 0, st>>>(bb.dkp, bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
+        bloglik_grad_reduce_kernel<<<ncn, 256, 0, st>>>(dpart, bb.dns, g, dgrad);
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipEventRecord(ctx->ev[5], st));
+        TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipMemcpyAsync(grad + c0 * 4, dgrad, (size_t)cn * 32, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipStreamSynchronize(st));
+        float t[4] = {0.f, 0.f, 0.f, 0.f};
+        TGP_HIP(hipEventElapsedTime(&t[0], ctx->ev[0], ctx->ev[1]));
+        TGP_HIP(hipEventElapsedTime(&t[1], ctx->ev[1], ctx->ev[2]));
+        TGP_HIP(hipEventElapsedTime(&t[2], ctx->ev[2], ctx->ev[3]));
+        TGP_HIP(hipEventElapsedTime(&t[3], ctx->ev[4], ctx->ev[5]));
+        ms_k += t[0];
+        ms_c += t[1];
+        ms_s += t[2];
+        ms_g += t[3];
+        rc = batch_collect(ctx, fn, bb, c0, cn, logdet, ydota, info);
+        if (rc) return rc;
+    }
+    for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
+    ctx->timings[0] = ms_k;
+    ctx->timings[1] = ms_c;
+    ctx->timings[2] = ms_s;
+    ctx->timings[3] = ms_g;
     return 0;
 }

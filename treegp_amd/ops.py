@@ -179,6 +179,33 @@ def gp_solve_batch(specs, Xs, ys, y_errs=None, want_alpha=True, ctx=None):
     return alphas, logdet, chi2, info.astype(np.int64)
 
 
+def gp_solve_grad_batch(specs, Xs, ys, y_errs=None, ctx=None):
+    """One evaluation of many gradient-driven fits in one launch sequence (tgp_gp_solve_grad_batch): gp_solve_batch plus, from
+    each problem's factor and alpha in the same call, d logL / d (log amp, a, b, c) as ``gp_loglik_grad`` gives it for one
+    problem.  Arguments as gp_solve_batch; Gaussian kernels only.  Returns (logdets (nb,), chi2 = y.alpha (nb,), g4 (nb, 4),
+    info (nb,) int): logdets and chi2 are bit for bit gp_solve_batch's, info[b] > 0 marks a problem whose other outputs are
+    meaningless, and each problem's result does not depend on the others in the call."""
+    specs = list(specs)
+    ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("gp_solve_grad_batch: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("gp_solve_grad_batch: problems of order up to %d, got %d (use gp_solve and gp_loglik_grad)"
+                         % (BATCH_NMAX, nmax))
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    logdet = np.empty(nb)
+    chi2 = np.empty(nb)
+    g4 = np.empty((nb, 4))
+    info = np.zeros(nb, dtype=np.int32)
+    rc = lib.tgp_gp_solve_grad_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(logdet),
+                                     ptr(chi2), ptr(g4), ptr(info))
+    check(ctx, rc, "tgp_gp_solve_grad_batch")
+    return logdet, chi2, g4, info.astype(np.int64)
+
+
 POSTERIOR_MMAX = {"var": 65280, "cov": 4096}    # tgp_gp_posterior_batch: query points per problem (the row grids of S3b / S3c)
 
 
