@@ -13,7 +13,6 @@ struct Arena {               // bump allocator over the ctx staging buffer (size
         return p;
     }
 };
-inline size_t rup(size_t b) { return (b + 255) / 256 * 256; }
 
 struct Staging {
     void *buf = nullptr;

@@ -6,6 +6,7 @@
 // launch covers all problems of the chunk, the problem index being the grid's y dimension, and runs the existing device
 // bodies through thin wrappers that only offset pointers by it:
 //   K build        kbuild_tile (kbuild_tile.h), once per kernel evaluator present
+//   posterior, gradient   the bodies of post_tile.h, which the single-problem kernels of cov.hip call too
 //   per panel k    potrf128_body (0,0) -> rows below: X = A W0^T -> A[:,128:] -= X L10^T -> potrf128_body (1,1) ->
 //                  rows below: X = A W1^T (gemm_tile_128) -> trailing update, depth 256 (gemm_tile_dtv)
 //   sweeps         one launch per 128-block and direction: the block's GEMV with W = L_jj^-1 and the update of the other blocks
@@ -18,6 +19,7 @@
 #include "kernel_eval.h"
 #include "kbuild_tile.h"
 #include "gemm_tile.h"
+#include "post_tile.h"
 #include "potrf128.h"
 
 namespace {
@@ -58,11 +60,8 @@ __global__ __launch_bounds__(256) void bkbuild_kernel(const KParams *__restrict_
                                                       const int64_t *__restrict__ ns, const double *__restrict__ X,
                                                       const double *__restrict__ e, BatchDims d, double *__restrict__ A) {
     const int b = list[blockIdx.y];
-    const int64_t t = blockIdx.x;
-    int64_t ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > t) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int64_t tj = t - ti * (ti + 1) / 2;
+    int64_t ti, tj;
+    tri_index(blockIdx.x, ti, tj);
     const int64_t pj = tj >> 1;
     double *tile = A + b * d.ae + panel_off(pj, d.Np) + (ti * TGP_TB - pj * TGP_PW) * TGP_PW + (tj & 1) * TGP_TB;
     const KParams p = kp[b];
@@ -88,18 +87,15 @@ __global__ __launch_bounds__(256, 2) void bgemm_col_kernel(double *A, const doub
 
 // trailing update after panel k: C(ti, tj) -= P[ti] P[tj]^T over the T x T lower tiles from block k + 1, depth 256
 __global__ __launch_bounds__(256, 2) void bsyrk_kernel(double *A, BatchDims d, int k, int T) {
-    const int64_t t = blockIdx.x;
-    int ti = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((int64_t)ti * (ti + 1) / 2 > t) --ti;
-    while ((int64_t)(ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int tj = (int)(t - (int64_t)ti * (ti + 1) / 2);
+    int64_t ti, tj;
+    tri_index(blockIdx.x, ti, tj);
     double *Ab = A + blockIdx.y * d.ae;
     const double *P = Ab + panel_off(k, d.Np) + (int64_t)TGP_PW * TGP_PW;      // panel k from row 256 (k + 1)
     const int ob = k + 1;
     const int64_t pj = ob + (tj >> 1);
-    const int64_t I = (int64_t)TGP_PW * ob + (int64_t)TGP_TB * ti;
+    const int64_t I = (int64_t)TGP_PW * ob + TGP_TB * ti;
     double *C = Ab + panel_off(pj, d.Np) + (I - pj * TGP_PW) * TGP_PW + (tj & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_PW, 1>(P + (int64_t)ti * TGP_TB * TGP_PW, P + (int64_t)tj * TGP_TB * TGP_PW, C, nullptr, nullptr);
+    gemm_tile_dtv<4, TGP_PW, 1>(P + ti * TGP_TB * TGP_PW, P + tj * TGP_TB * TGP_PW, C, nullptr, nullptr);
 }
 
 // ---- sweeps: GEMV pieces on 128-blocks --------------------------------------------------------------------------------------
@@ -208,7 +204,7 @@ __global__ __launch_bounds__(256) void bfinish_kernel(const double *__restrict__
     }
 }
 
-// ---- posterior of every problem (seam S3f): S3b / S3c of cov.hip with the problem index on the grid -------------------------
+// ---- posterior of every problem (seam S3f): S3b / S3c of cov.hip with the problem index on the grid (post_tile.h) -----------
 // Problem b's query rows live in the 256-wide panel layout of cov.hip's Bt: Bt_b (Mp x Np) at b * Mp * Np, panel p at
 // + p * Mp * 256; the covariance's C_b (Mp x Mp) at b * Mp * Mp in the same layout.  Tile forms and summation depths depend on
 // kb, Np and Mp only.  Row tiles at or beyond m_b and column blocks at or beyond n_b are zero from the start and stay zero, so a
@@ -234,40 +230,30 @@ __global__ __launch_bounds__(256) void bcross_kernel(const KParams *__restrict__
     const double *xs = Xs + (int64_t)b * 2 * q.mmax;
     const double *x = self ? xs : X + (int64_t)b * 2 * Np;
     const KParams p = kp[b];
-    double v = 0.0;
-    if (i < m && j < n) {
-        v = kernel_value<KE>(p, xs[2 * i] - x[2 * j], xs[2 * i + 1] - x[2 * j + 1]);
-        if (self && i == j) v = p.amp;
-    }
-    out[(int64_t)b * q.Mp * ncols + (j >> 8) * q.Mp * TGP_PW + i * TGP_PW + (j & 255)] = v;
+    out[(int64_t)b * q.Mp * ncols + panel_elem(i, j, q.Mp)] = cross_value<KE>(p, xs, m, x, n, self, i, j);
 }
 
-// Bt_b[:, kb] <- Bt_b[:, kb] W_kb^T, one 128-row tile per workgroup (cov_trsm_kernel)
+// Bt_b[:, kb] <- Bt_b[:, kb] W_kb^T, one 128-row tile per workgroup
 __global__ __launch_bounds__(256, 2) void btrsm_kernel(double *Bt, const double *W, const int64_t *__restrict__ ns,
                                                        const int64_t *__restrict__ ms, BatchDims d, PostDims q, int kb) {
     const int b = blockIdx.y;
     const int64_t t = blockIdx.x;
     if (t * TGP_TB >= ms[b] || (int64_t)kb * TGP_TB >= ns[b]) return;
     double *Bk = Bt + (int64_t)b * q.Mp * d.Np + (int64_t)(kb >> 1) * q.Mp * TGP_PW + (kb & 1) * TGP_TB + t * TGP_TB * TGP_PW;
-    gemm_tile_128<0, TGP_TB, TGP_TB>(Bk, W + b * d.we + (int64_t)kb * TGP_TB * TGP_TB, Bk);
+    post_trsm_tile(Bk, W + b * d.we + (int64_t)kb * TGP_TB * TGP_TB);
 }
 
-// Bt_b[:, c] -= Bt_b[:, kb] L_b[c, kb]^T for c = kb + 1 + blockIdx.x / mt, row tile blockIdx.x % mt (cov_update_kernel)
+// Bt_b[:, c] -= Bt_b[:, kb] L_b[c, kb]^T for c = kb + 1 + blockIdx.x / mt, row tile blockIdx.x % mt
 __global__ __launch_bounds__(256, 2) void bupdate_kernel(double *Bt, const double *A, const int64_t *__restrict__ ns,
                                                          const int64_t *__restrict__ ms, BatchDims d, PostDims q, int kb, int mt) {
     const int b = blockIdx.y;
     const int64_t ti = blockIdx.x % mt;
     const int64_t c = kb + 1 + blockIdx.x / mt;
     if (ti * TGP_TB >= ms[b] || c * TGP_TB >= ns[b]) return;
-    const int64_t p = kb >> 1;
-    double *Btb = Bt + (int64_t)b * q.Mp * d.Np;
-    const double *a = Btb + p * q.Mp * TGP_PW + ti * TGP_TB * TGP_PW + (kb & 1) * TGP_TB;
-    const double *l = A + b * d.ae + panel_off(p, d.Np) + (c * TGP_TB - p * TGP_PW) * TGP_PW + (kb & 1) * TGP_TB;
-    double *cc = Btb + (c >> 1) * q.Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_TB, 1>(a, l, cc, nullptr, nullptr);
+    post_update_tile(Bt + (int64_t)b * q.Mp * d.Np, q.Mp, A + b * d.ae, d.Np, kb, 0, ti, c);
 }
 
-// var_b[i] = amp_b - |Bt_b[i, :]|^2 over all Np / 256 panels, one wave per row as var_rows_kernel; rows >= m_b are 0
+// var_b[i] = amp_b - |Bt_b[i, :]|^2 over all Np / 256 panels, one wave per row (row_sqnorm_wave); rows >= m_b are 0
 __global__ __launch_bounds__(256) void bvar_rows_kernel(const double *__restrict__ Bt, const KParams *__restrict__ kp,
                                                         const int64_t *__restrict__ ms, int64_t Np, PostDims q,
                                                         double *__restrict__ var) {
@@ -280,29 +266,17 @@ __global__ __launch_bounds__(256) void bvar_rows_kernel(const double *__restrict
         if (lane == 0) *out = 0.0;
         return;
     }
-    const int nP = (int)(Np / TGP_PW);
-    const double *row = Bt + (int64_t)b * q.Mp * Np + i * TGP_PW + 2 * lane;
-    double acc = 0.0;
-#pragma unroll 4
-    for (int p = 0; p < nP; ++p) {
-        const double2 a = *(const double2 *)(row + (int64_t)p * q.Mp * TGP_PW);
-        const double2 c = *(const double2 *)(row + (int64_t)p * q.Mp * TGP_PW + 128);
-        acc += (a.x * a.x + a.y * a.y) + (c.x * c.x + c.y * c.y);
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    const double acc = row_sqnorm_wave(Bt + (int64_t)b * q.Mp * Np, q.Mp, (int)(Np / TGP_PW), i);
     if (lane == 0) *out = kp[b].amp - acc;
 }
 
-// C_b(ti, tj) -= sum over all panels of Bt_b[ti] Bt_b[tj]^T (cov_syrk_kernel); blockIdx.x = ti + mt * tj
+// C_b(ti, tj) -= sum over all panels of Bt_b[ti] Bt_b[tj]^T; blockIdx.x = ti + mt * tj
 __global__ __launch_bounds__(256, 2) void bsyrk_cov_kernel(double *C, const double *Bt, const int64_t *__restrict__ ms, int64_t Np,
                                                            PostDims q, int mt) {
     const int b = blockIdx.y;
     const int64_t ti = blockIdx.x % mt, tj = blockIdx.x / mt;
     if (ti * TGP_TB >= ms[b] || tj * TGP_TB >= ms[b]) return;
-    const double *Btb = Bt + (int64_t)b * q.Mp * Np;
-    double *c = C + (int64_t)b * q.Mp * q.Mp + (tj >> 1) * q.Mp * TGP_PW + ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_PW, 0>(Btb + ti * TGP_TB * TGP_PW, Btb + tj * TGP_TB * TGP_PW, c, nullptr, nullptr, (int)(Np / TGP_PW),
-                                q.Mp * TGP_PW, q.Mp * TGP_PW);
+    post_syrk_tile(C + (int64_t)b * q.Mp * q.Mp, Bt + (int64_t)b * q.Mp * Np, q.Mp, (int)(Np / TGP_PW), ti, tj, 0);
 }
 
 // C_b (panels) -> the caller's (nb, mmax, mmax), exactly 0 outside m_b x m_b; blockIdx.x = 256-column group + groups * row
@@ -315,10 +289,10 @@ __global__ __launch_bounds__(256) void bunpad_cov_kernel(const double *__restric
     if (j >= q.mmax) return;
     const int64_t m = ms[b];
     out[((int64_t)b * q.mmax + i) * q.mmax + j] =
-        (i < m && j < m) ? C[(int64_t)b * q.Mp * q.Mp + (j >> 8) * q.Mp * TGP_PW + i * TGP_PW + (j & 255)] : 0.0;
+        (i < m && j < m) ? C[(int64_t)b * q.Mp * q.Mp + panel_elem(i, j, q.Mp)] : 0.0;
 }
 
-// ---- likelihood gradient of every problem (seam S2f): S2d of cov.hip with the problem index on the grid ------------------------
+// ---- likelihood gradient of every problem (seam S2f): S2d of cov.hip with the problem index on the grid (post_tile.h) ----------
 // Problem b's Bt_b = L_b^-T and C_b = -K_b^-1 are Np x Np in the 256-wide panel layout of cov.hip (Bt_b at b * Np * Np, panel p
 // at + p * Np * 256).  Bt_b starts as the identity and is upper triangular: row tile ti is zero left of column block ti, so the
 // substitution's step kb covers the row tiles ti <= kb only (btrsm_kernel / bupdate_kernel above with kb + 1 row tiles, ms = ns)
@@ -353,92 +327,38 @@ __global__ __launch_bounds__(256) void bgrad_init_kernel(double *__restrict__ Bt
     }
 }
 
-// lower tile pairs (ti >= tj), linear in blockIdx.x: C_b(ti, tj) = -sum_{p >= ti / 2} Bt_b[ti][p] Bt_b[tj][p]^T (kinv_syrk_kernel)
+// lower tile pairs (ti >= tj), linear in blockIdx.x: C_b(ti, tj) = -sum_{p >= ti / 2} Bt_b[ti][p] Bt_b[tj][p]^T
 __global__ __launch_bounds__(256, 2) void bkinv_syrk_kernel(double *C, const double *Bt, const int64_t *__restrict__ ns, int64_t Np, int nP) {
     const int b = blockIdx.y;
-    const int64_t t = blockIdx.x;
-    int64_t ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > t) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int64_t tj = t - ti * (ti + 1) / 2;
+    int64_t ti, tj;
+    tri_index(blockIdx.x, ti, tj);
     if (ti * TGP_TB >= ns[b]) return;
-    const int64_t p0 = ti >> 1;
-    const double *Btb = Bt + (int64_t)b * Np * Np + p0 * Np * TGP_PW;
-    double *c = C + (int64_t)b * Np * Np + (tj >> 1) * Np * TGP_PW + ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_PW, 0>(Btb + ti * TGP_TB * TGP_PW, Btb + tj * TGP_TB * TGP_PW, c, nullptr, nullptr, nP - (int)p0, Np * TGP_PW,
-                                Np * TGP_PW);
+    post_syrk_tile(C + (int64_t)b * Np * Np, Bt + (int64_t)b * Np * Np, Np, nP, ti, tj, ti >> 1);
 }
 
-// loglik_grad_kernel's body for problem b = blockIdx.y: 64 rows (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the
+// loglik_grad_block for problem b = blockIdx.y: 64 rows (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the
 // lower triangle below n_b, four partial sums per workgroup at partial[(b * nrb * nP + blockIdx.x) * 4]
 __global__ __launch_bounds__(256) void bloglik_grad_kernel(const KParams *__restrict__ kp, const int64_t *__restrict__ ns,
                                                            const double *__restrict__ X, const double *__restrict__ alpha,
                                                            const double *__restrict__ C, int64_t Np, GradDims g,
                                                            double *__restrict__ partial) {
-    __shared__ double red[4][4];
-    const int b = blockIdx.y, tid = threadIdx.x;
+    const int b = blockIdx.y;
     const int64_t n = ns[b];
     const int64_t pj = blockIdx.x % g.nP, i0 = (int64_t)(blockIdx.x / g.nP) * 64;
     if (i0 >= n || pj * TGP_PW >= n) return;                      // whole workgroups leave together; never summed
     const KParams p = kp[b];
-    const double *Xb = X + (int64_t)b * 2 * Np, *ab = alpha + (int64_t)b * Np;
-    const int64_t j = pj * TGP_PW + tid;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    if (pj * TGP_PW <= i0 + 63 && j < n) {
-        const double xj = Xb[2 * j], yj = Xb[2 * j + 1], aj = ab[j];
-        const double *col = C + (int64_t)b * Np * Np + pj * Np * TGP_PW + tid;
-        for (int r = 0; r < 64; ++r) {
-            const int64_t i = i0 + r;
-            if (i >= n) break;
-            if (j > i) continue;
-            const double m = ab[i] * aj + col[i * TGP_PW];          // alpha_i alpha_j - [K^-1]_ij   (C holds -K^-1)
-            if (i == j) {
-                acc[0] += 0.5 * m * p.amp;                          // the pair (i, i) counts once, d K_ii / d log amp = amp
-            } else {
-                const double dx = Xb[2 * i] - xj, dy = Xb[2 * i + 1] - yj;
-                const double e = p.amp * exp(-0.5 * quad_form(p, dx, dy)) * m;
-                acc[0] += e;
-                acc[1] -= 0.5 * e * dx * dx;
-                acc[2] -= e * dx * dy;
-                acc[3] -= 0.5 * e * dy * dy;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double v = acc[q];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if ((tid & 63) == 0) red[tid >> 6][q] = v;
-    }
-    __syncthreads();
-    if (tid < 4) partial[(((int64_t)b * g.nrb * g.nP) + blockIdx.x) * 4 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    loglik_grad_block(p, X + (int64_t)b * 2 * Np, alpha + (int64_t)b * Np, C + (int64_t)b * Np * Np, Np, n, pj, i0,
+                      partial + (((int64_t)b * g.nrb * g.nP) + blockIdx.x) * 4);
 }
 
 // one workgroup per problem: its partial sums (row blocks below n_b x panels below n_b, that order) in a fixed order that depends
 // on n_b alone
 __global__ __launch_bounds__(256) void bloglik_grad_reduce_kernel(const double *__restrict__ partial, const int64_t *__restrict__ ns,
                                                                   GradDims g, double *__restrict__ out) {
-    __shared__ double red[256][4];
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int b = blockIdx.x;
     const int64_t n = ns[b];
-    const int64_t nrb = (n + 63) / 64, nP = (n + TGP_PW - 1) / TGP_PW;
-    const double *pb = partial + (int64_t)b * g.nrb * g.nP * 4;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t q = tid; q < nrb * nP; q += 256) {
-        const int64_t rb = q / nP, p = q % nP;
-        for (int s = 0; s < 4; ++s) acc[s] += pb[(rb * g.nP + p) * 4 + s];
-    }
-    for (int s = 0; s < 4; ++s) red[tid][s] = acc[s];
-    __syncthreads();
-    for (int step = 128; step > 0; step >>= 1) {
-        if (tid < step)
-            for (int s = 0; s < 4; ++s) red[tid][s] += red[tid + step][s];
-        __syncthreads();
-    }
-    if (tid < 4) out[(int64_t)b * 4 + tid] = red[0][tid];
+    loglik_grad_reduce(partial + (int64_t)b * g.nrb * g.nP * 4, (n + 63) / 64, (n + TGP_PW - 1) / TGP_PW, g.nP, out + (int64_t)b * 4);
 }
-
-inline size_t rup(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -632,55 +552,97 @@ static int batch_collect(tgp_ctx *ctx, const char *fn, const BatchBufs &bb, int6
     return 0;
 }
 
-int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
-                       const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
-    static const char *fn = "tgp_gp_solve_batch";
-    if (!ctx) return -1;
-    if (nb < 1) { ctx->err = "tgp_gp_solve_batch: nb must be >= 1"; return -1; }
-    if (nmax < 1 || nmax > 4096) { ctx->err = "tgp_gp_solve_batch: nmax must be in 1 .. 4096 (larger problems: tgp_gp_solve)"; return -1; }
-    TGP_ARG(ks && ns && X && y && logdet && info);
+// One batched call: the geometry, the caller's host arrays of S2e, the chunk size, the arena with S2e's arrays taken (the caller
+// takes its own behind them with take()) and the phase times summed over the chunks.
+struct BatchRun {
+    tgp_ctx *ctx;
+    const char *fn;
+    int nb;
+    int64_t nmax;
+    double *alpha, *logdet, *ydota;
+    int32_t *info;
+    BatchDims d;
+    int64_t C;          // problems per chunk
+    char *base;
+    size_t off;
+    BatchBufs bb;
+    double ms[5];       // K build, Cholesky, sweeps, the caller's device work (ev[4] .. ev[5]), its result's transfer (ev[5] .. ev[6])
+    void *take(size_t bytes) { void *p = base + off; off += rup(bytes); return p; }
+};
+
+// after the caller's own NULL checks: nb, nmax, ns and the kinds (batch_check), then the geometry.  Touches no device.
+static int batch_begin(BatchRun &r, tgp_ctx *ctx, const char *fn, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+                       double *alpha, double *logdet, double *ydota, int32_t *info) {
     int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
     if (rc) return rc;
-    TGP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW;
-    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
-    const size_t per = batch_bytes_per_problem(d, nmax);
-    const size_t fixed = 8 * 256;
-    const int64_t C = batch_chunk(ctx, fn, nb, per, fixed, &rc);
-    if (rc) return rc;
-    // one arena per chunk size: arrays of C problems each
-    rc = tgp_ensure_scratch(ctx, (size_t)C * per + fixed);
-    if (rc) return rc;
-    size_t off = 0;
-    BatchBufs bb;
-    rc = batch_take(ctx, d, nmax, C, (char *)ctx->scratch, &off, &bb);
-    if (rc) return rc;
+    const int64_t Np = padded_n(nmax);
+    r = BatchRun{ctx, fn, nb, nmax, alpha, logdet, ydota, info, {Np, panel_off(Np / TGP_PW, Np), Np * TGP_TB}};
+    return 0;
+}
 
-    double ms_k = 0.0, ms_c = 0.0, ms_s = 0.0;
-    for (int64_t c0 = 0; c0 < nb; c0 += C) {
-        const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
-        rc = batch_factor_chunk(ctx, d, bb, c0, cn, ks, ns, nmax, X, y, yerr, alpha != nullptr);
+// the chunk size for S2e's bytes per problem plus the caller's `extra`, one arena per chunk size (arrays of C problems each),
+// S2e's arrays taken from it
+static int batch_arena(BatchRun &r, size_t extra) {
+    tgp_ctx *ctx = r.ctx;
+    TGP_HIP(hipSetDevice(ctx->device));
+    const size_t per = batch_bytes_per_problem(r.d, r.nmax) + extra;
+    const size_t fixed = 8 * 256;
+    int rc = 0;
+    r.C = batch_chunk(ctx, r.fn, r.nb, per, fixed, &rc);
+    if (rc) return rc;
+    rc = tgp_ensure_scratch(ctx, (size_t)r.C * per + fixed);
+    if (rc) return rc;
+    r.base = (char *)ctx->scratch;
+    r.off = 0;
+    return batch_take(ctx, r.d, r.nmax, r.C, r.base, &r.off, &r.bb);
+}
+
+// End of chunk c0 .. c0 + cn: info, logdet / chi2, alpha (when asked for) and the caller's result (`res`, or NULL) to the host, in
+// that order; next = 2 records ev[6] behind them.  Synchronises the stream, adds the chunk's phase times (ev[0] .. ev[3] and the
+// caller's `next` intervals from ev[4] on) and hands info, logdet and chi2 to the caller's arrays.
+static int batch_end_chunk(BatchRun &r, int64_t c0, int64_t cn, void *res, const void *dres, size_t res_bytes, int next) {
+    tgp_ctx *ctx = r.ctx;
+    hipStream_t st = ctx->stream;
+    const BatchBufs &bb = r.bb;
+    TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
+    TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
+    if (r.alpha) TGP_HIP(hipMemcpyAsync(r.alpha + c0 * r.nmax, bb.ra, (size_t)cn * r.nmax * 8, hipMemcpyDeviceToHost, st));
+    if (res) TGP_HIP(hipMemcpyAsync(res, dres, res_bytes, hipMemcpyDeviceToHost, st));
+    if (next == 2) TGP_HIP(hipEventRecord(ctx->ev[6], st));
+    TGP_HIP(hipStreamSynchronize(st));
+    static const int from[5] = {0, 1, 2, 4, 5};
+    for (int i = 0; i < 3 + next; ++i) {
+        float t = 0.f;
+        TGP_HIP(hipEventElapsedTime(&t, ctx->ev[from[i]], ctx->ev[from[i] + 1]));
+        r.ms[i] += t;
+    }
+    return batch_collect(ctx, r.fn, bb, c0, cn, r.logdet, r.ydota, r.info);
+}
+
+// only the slots a batched call fills: nothing of an earlier call on the context is left behind in the others
+static void batch_finish(const BatchRun &r) {
+    static const int slot[5] = {0, 1, 2, 3, 9};
+    for (int i = 0; i < TGP_NTIMINGS; ++i) r.ctx->timings[i] = 0.0;
+    for (int i = 0; i < 5; ++i) r.ctx->timings[slot[i]] = r.ms[i];
+}
+
+int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                       const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
+    if (!ctx) return -1;
+    TGP_ARG(ks && ns && X && y && logdet && info);
+    BatchRun r;
+    int rc = batch_begin(r, ctx, "tgp_gp_solve_batch", nb, ks, ns, nmax, alpha, logdet, ydota, info);
+    if (rc) return rc;
+    rc = batch_arena(r, 0);
+    if (rc) return rc;
+    for (int64_t c0 = 0; c0 < nb; c0 += r.C) {
+        const int64_t cn = (nb - c0) < r.C ? (nb - c0) : r.C;
+        rc = batch_factor_chunk(ctx, r.d, r.bb, c0, cn, ks, ns, nmax, X, y, yerr, alpha != nullptr);
         if (rc) return rc;
-        TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
-        if (alpha) TGP_HIP(hipMemcpyAsync(alpha + c0 * nmax, bb.ra, (size_t)cn * nmax * 8, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipStreamSynchronize(st));
-        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-        TGP_HIP(hipEventElapsedTime(&t0, ctx->ev[0], ctx->ev[1]));
-        TGP_HIP(hipEventElapsedTime(&t1, ctx->ev[1], ctx->ev[2]));
-        TGP_HIP(hipEventElapsedTime(&t2, ctx->ev[2], ctx->ev[3]));
-        ms_k += t0;
-        ms_c += t1;
-        ms_s += t2;
-        rc = batch_collect(ctx, fn, bb, c0, cn, logdet, ydota, info);
+        rc = batch_end_chunk(r, c0, cn, nullptr, nullptr, 0, 0);
         if (rc) return rc;
     }
-    // only the slots this call fills: nothing of an earlier call on the context is left behind in the others
-    for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
-    ctx->timings[0] = ms_k;
-    ctx->timings[1] = ms_c;
-    ctx->timings[2] = ms_s;
+    batch_finish(r);
     ctx->timings[10] = alpha ? 2.0 : 1.0;
     return 0;
 }
@@ -689,7 +651,7 @@ int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t
 // Per chunk, after batch_factor_chunk: H_b into Bt_b (and Kss_b into C_b), the block substitution Bt_b <- H_b L_b^-T over the
 // 128-column blocks kb (trsm with W_kb, update of the blocks to its right), then amp_b - |Bt_b[i, :]|^2 or Kss_b - Bt_b Bt_b^T,
 // unpadded to the caller's layout on the device.
-#define TGP_POST_VAR_MMAX 65280       // the row grids of cov.hip (largest multiple of 256 <= 65 535)
+#define TGP_POST_VAR_MMAX TGP_VAR_CHUNK_MAX       // the variance's rows go through a row grid, as in cov.hip
 #define TGP_POST_COV_MMAX 4096
 
 int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
@@ -705,7 +667,8 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
         ctx->err = "tgp_gp_posterior_batch: what = " + std::to_string(what) + " is neither 1 (variance) nor 2 (covariance)";
         return -1;
     }
-    int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
+    BatchRun r;
+    int rc = batch_begin(r, ctx, fn, nb, ks, ns, nmax, alpha, logdet, ydota, info);
     if (rc) return rc;
     const bool cov = what == 2;
     const int64_t mlim = cov ? TGP_POST_COV_MMAX : TGP_POST_VAR_MMAX;
@@ -719,34 +682,24 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
                        std::to_string((long long)mmax);
             return -1;
         }
-    TGP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW, nT = Np / TGP_TB;
-    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
+    const BatchDims &d = r.d;
+    const int64_t Np = d.Np, nT = Np / TGP_TB;
     const PostDims q{(mmax + TGP_PW - 1) / TGP_PW * TGP_PW, mmax};
     const int mt = (int)(q.Mp / TGP_TB);
-    // per problem: S2e's arrays, Bt, the query rows, ms, the result on the device (panels for the covariance) and unpadded
+    // per problem beside S2e's arrays: Bt, the query rows, ms, the result on the device (panels for the covariance) and unpadded
     const size_t out_elems = cov ? (size_t)mmax * mmax : (size_t)mmax;
-    const size_t per = batch_bytes_per_problem(d, nmax) + rup((size_t)q.Mp * Np * 8) + rup((size_t)mmax * 16) + rup(8) +
-                       (cov ? rup((size_t)q.Mp * q.Mp * 8) : 0) + rup(out_elems * 8);
-    const size_t fixed = 8 * 256;
-    const int64_t C = batch_chunk(ctx, fn, nb, per, fixed, &rc);
+    rc = batch_arena(r, rup((size_t)q.Mp * Np * 8) + rup((size_t)mmax * 16) + rup(8) + (cov ? rup((size_t)q.Mp * q.Mp * 8) : 0) +
+                            rup(out_elems * 8));
     if (rc) return rc;
-    rc = tgp_ensure_scratch(ctx, (size_t)C * per + fixed);
-    if (rc) return rc;
-    char *base = (char *)ctx->scratch;
-    size_t off = 0;
-    BatchBufs bb;
-    rc = batch_take(ctx, d, nmax, C, base, &off, &bb);
-    if (rc) return rc;
-    auto take = [&](size_t bytes) { void *p = base + off; off += rup(bytes); return p; };
-    double *dBt = (double *)take((size_t)C * q.Mp * Np * 8);
-    double *dXs = (double *)take((size_t)C * mmax * 16);
-    int64_t *dms = (int64_t *)take((size_t)C * 8);
-    double *dC = cov ? (double *)take((size_t)C * q.Mp * q.Mp * 8) : nullptr;
-    double *dU = (double *)take((size_t)C * out_elems * 8);
+    const int64_t C = r.C;
+    BatchBufs &bb = r.bb;
+    double *dBt = (double *)r.take((size_t)C * q.Mp * Np * 8);
+    double *dXs = (double *)r.take((size_t)C * mmax * 16);
+    int64_t *dms = (int64_t *)r.take((size_t)C * 8);
+    double *dC = cov ? (double *)r.take((size_t)C * q.Mp * q.Mp * 8) : nullptr;
+    double *dU = (double *)r.take((size_t)C * out_elems * 8);
 
-    double ms_k = 0.0, ms_c = 0.0, ms_s = 0.0, ms_p = 0.0, ms_t = 0.0;
     for (int64_t c0 = 0; c0 < nb; c0 += C) {
         const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
         const unsigned ncn = (unsigned)cn;
@@ -781,44 +734,16 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
         }
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[5], st));
-        TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
-        if (alpha) TGP_HIP(hipMemcpyAsync(alpha + c0 * nmax, bb.ra, (size_t)cn * nmax * 8, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipMemcpyAsync(unc + (size_t)c0 * out_elems, dU, (size_t)cn * out_elems * 8, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipEventRecord(ctx->ev[6], st));
-        TGP_HIP(hipStreamSynchronize(st));
-        float t[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        TGP_HIP(hipEventElapsedTime(&t[0], ctx->ev[0], ctx->ev[1]));
-        TGP_HIP(hipEventElapsedTime(&t[1], ctx->ev[1], ctx->ev[2]));
-        TGP_HIP(hipEventElapsedTime(&t[2], ctx->ev[2], ctx->ev[3]));
-        TGP_HIP(hipEventElapsedTime(&t[3], ctx->ev[4], ctx->ev[5]));
-        TGP_HIP(hipEventElapsedTime(&t[4], ctx->ev[5], ctx->ev[6]));
-        ms_k += t[0];
-        ms_c += t[1];
-        ms_s += t[2];
-        ms_p += t[3];
-        ms_t += t[4];
-        rc = batch_collect(ctx, fn, bb, c0, cn, logdet, ydota, info);
+        rc = batch_end_chunk(r, c0, cn, unc + (size_t)c0 * out_elems, dU, (size_t)cn * out_elems * 8, 2);
         if (rc) return rc;
     }
-    for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
-    ctx->timings[0] = ms_k;
-    ctx->timings[1] = ms_c;
-    ctx->timings[2] = ms_s;
-    ctx->timings[3] = ms_p;
-    ctx->timings[9] = ms_t;
+    batch_finish(r);
     return 0;
 }
 
 // ---- S2f: the likelihood gradient of every problem of S2e from its factor and alpha, in the same call ---------------------------
 // Per chunk, after batch_factor_chunk with both sweeps: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row
 // tiles, C_b = -Bt_b Bt_b^T over the lower tile pairs, the reduction against dK/dp and one fixed-order sum per problem.
-// per problem beside S2e's arrays: Bt and C (Np x Np each), the reduction's partial sums, the four results
-static size_t grad_bytes_per_problem(const BatchDims &d, int64_t nmax) {
-    const size_t nparts = (size_t)(d.Np / 64) * (size_t)(d.Np / TGP_PW);
-    return batch_bytes_per_problem(d, nmax) + 2 * rup((size_t)d.Np * d.Np * 8) + rup(nparts * 32) + rup(32);
-}
-
 int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
                             const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
     static const char *fn = "tgp_gp_solve_grad_batch";
@@ -827,7 +752,8 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
         ctx->err = "tgp_gp_solve_grad_batch: ks, ns, X, y, logdet, grad and info must not be NULL";
         return -1;
     }
-    int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
+    BatchRun r;
+    int rc = batch_begin(r, ctx, fn, nb, ks, ns, nmax, nullptr, logdet, ydota, info);
     if (rc) return rc;
     for (int b = 0; b < nb; ++b)
         if (kind_to_ke(ks[b].kind) != KE_GAUSS) {
@@ -836,30 +762,21 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
                        "(treegp/kernels.py:128-150)";
             return -1;
         }
-    TGP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int64_t Np = padded_n(nmax), nP = Np / TGP_PW, nT = Np / TGP_TB;
-    const BatchDims d{Np, panel_off(nP, Np), Np * TGP_TB};
+    const BatchDims &d = r.d;
+    const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
     const PostDims q{Np, nmax};                                   // Bt_b is square: the "query rows" are the problem's own
     const GradDims g{Np / 64, nP};
-    const size_t per = grad_bytes_per_problem(d, nmax);
-    const size_t fixed = 8 * 256;
-    const int64_t C = batch_chunk(ctx, fn, nb, per, fixed, &rc);
+    // per problem beside S2e's arrays: Bt and C (Np x Np each), the reduction's partial sums, the four results
+    rc = batch_arena(r, 2 * rup((size_t)Np * Np * 8) + rup((size_t)(g.nrb * g.nP) * 32) + rup(32));
     if (rc) return rc;
-    rc = tgp_ensure_scratch(ctx, (size_t)C * per + fixed);
-    if (rc) return rc;
-    char *base = (char *)ctx->scratch;
-    size_t off = 0;
-    BatchBufs bb;
-    rc = batch_take(ctx, d, nmax, C, base, &off, &bb);
-    if (rc) return rc;
-    auto take = [&](size_t bytes) { void *p = base + off; off += rup(bytes); return p; };
-    double *dBt = (double *)take((size_t)C * Np * Np * 8);
-    double *dC = (double *)take((size_t)C * Np * Np * 8);
-    double *dpart = (double *)take((size_t)C * g.nrb * g.nP * 32);
-    double *dgrad = (double *)take((size_t)C * 32);
+    const int64_t C = r.C;
+    BatchBufs &bb = r.bb;
+    double *dBt = (double *)r.take((size_t)C * Np * Np * 8);
+    double *dC = (double *)r.take((size_t)C * Np * Np * 8);
+    double *dpart = (double *)r.take((size_t)C * g.nrb * g.nP * 32);
+    double *dgrad = (double *)r.take((size_t)C * 32);
 
-    double ms_k = 0.0, ms_c = 0.0, ms_s = 0.0, ms_g = 0.0;
     for (int64_t c0 = 0; c0 < nb; c0 += C) {
         const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
         const unsigned ncn = (unsigned)cn;
@@ -879,26 +796,9 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
         bloglik_grad_reduce_kernel<<<ncn, 256, 0, st>>>(dpart, bb.dns, g, dgrad);
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[5], st));
-        TGP_HIP(hipMemcpyAsync(bb.hinfo, bb.dinfo, (size_t)cn * 4, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipMemcpyAsync(bb.hout, bb.dout, (size_t)cn * 16, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipMemcpyAsync(grad + c0 * 4, dgrad, (size_t)cn * 32, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipStreamSynchronize(st));
-        float t[4] = {0.f, 0.f, 0.f, 0.f};
-        TGP_HIP(hipEventElapsedTime(&t[0], ctx->ev[0], ctx->ev[1]));
-        TGP_HIP(hipEventElapsedTime(&t[1], ctx->ev[1], ctx->ev[2]));
-        TGP_HIP(hipEventElapsedTime(&t[2], ctx->ev[2], ctx->ev[3]));
-        TGP_HIP(hipEventElapsedTime(&t[3], ctx->ev[4], ctx->ev[5]));
-        ms_k += t[0];
-        ms_c += t[1];
-        ms_s += t[2];
-        ms_g += t[3];
-        rc = batch_collect(ctx, fn, bb, c0, cn, logdet, ydota, info);
+        rc = batch_end_chunk(r, c0, cn, grad + c0 * 4, dgrad, (size_t)cn * 32, 1);
         if (rc) return rc;
     }
-    for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
-    ctx->timings[0] = ms_k;
-    ctx->timings[1] = ms_c;
-    ctx->timings[2] = ms_s;
-    ctx->timings[3] = ms_g;
+    batch_finish(r);
     return 0;
 }

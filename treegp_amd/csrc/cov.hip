@@ -13,6 +13,7 @@
 #include "tgp_internal.h"
 #include "kernel_eval.h"
 #include "gemm_tile.h"
+#include "post_tile.h"
 
 namespace {
 // out: panels of 256 columns, panel p at out + p * rows * 256, element (i, j) -> [i][j & 255]
@@ -23,12 +24,7 @@ __global__ __launch_bounds__(256) void cross_panels_kernel(KParams p, const doub
     const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t i = blockIdx.y;
     if (j >= ncols) return;
-    double v = 0.0;
-    if (i < m && j < n) {
-        v = kernel_value<KE>(p, Xs[2 * i] - X[2 * j], Xs[2 * i + 1] - X[2 * j + 1]);
-        if (self && i == j) v = p.amp;
-    }
-    out[(j >> 8) * rows * TGP_PW + i * TGP_PW + (j & 255)] = v;
+    out[panel_elem(i, j, rows)] = cross_value<KE>(p, Xs, m, X, n, self, i, j);
 }
 
 int launch_cross_panels(tgp_ctx *ctx, const tgp_kernel *k, const double *d_Xs, int64_t m, const double *d_X, int64_t n,
@@ -49,19 +45,13 @@ int launch_cross_panels(tgp_ctx *ctx, const tgp_kernel *k, const double *d_Xs, i
 // Bt[:, kb] <- Bt[:, kb] W_kb^T      (one 128-row tile per workgroup)
 __global__ __launch_bounds__(256, 2) void cov_trsm_kernel(double *Bk, const double *W) {
     const int64_t t = blockIdx.x;
-    gemm_tile_128<0, TGP_TB, TGP_TB>(Bk + t * TGP_TB * TGP_PW, W, Bk + t * TGP_TB * TGP_PW);
+    post_trsm_tile(Bk + t * TGP_TB * TGP_PW, W);
 }
 
 // Bt[:, c] -= Bt[:, kb] L[c, kb]^T for c = kb + 1 + blockIdx.y
 // Bt holds the panels from pb on (panel p at Bt + (p - pb) * Mp * 256; pb = 0 but for tgp_factor_inv_diag's chunks)
 __global__ __launch_bounds__(256, 2) void cov_update_kernel(double *Bt, int64_t Mp, const double *A, int64_t Np, int kb, int64_t pb) {
-    const int64_t ti = blockIdx.x;
-    const int64_t c = kb + 1 + blockIdx.y;
-    const int64_t p = kb >> 1;
-    const double *a = Bt + (p - pb) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (kb & 1) * TGP_TB;
-    const double *b = A + panel_off(p, Np) + (c * TGP_TB - p * TGP_PW) * TGP_PW + (kb & 1) * TGP_TB;
-    double *cc = Bt + ((c >> 1) - pb) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (c & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_TB, 1>(a, b, cc, nullptr, nullptr);
+    post_update_tile(Bt, Mp, A, Np, kb, pb, blockIdx.x, kb + 1 + blockIdx.y);
 }
 
 // ---- the substitution in steps of S = 1024 (512) columns, with the factor's inverse slabs (trsv_big.hip) -------------------------
@@ -97,10 +87,7 @@ __global__ __launch_bounds__(256, 2) void cov_update_big_kernel(double *Bt, int6
 
 // C(ti, tj) -= sum over all panels of Bt[ti] Bt[tj]^T        (C in the same panel layout, Mp rows)
 __global__ __launch_bounds__(256, 2) void cov_syrk_kernel(double *Cpm, const double *Bt, int64_t Mp, int nP) {
-    const int64_t ti = blockIdx.x, tj = blockIdx.y;
-    double *c = Cpm + (tj >> 1) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_PW, 0>(Bt + ti * TGP_TB * TGP_PW, Bt + tj * TGP_TB * TGP_PW, c, nullptr, nullptr, nP, Mp * TGP_PW,
-                                Mp * TGP_PW);
+    post_syrk_tile(Cpm, Bt, Mp, nP, blockIdx.x, blockIdx.y, 0);
 }
 }  // namespace
 
@@ -122,7 +109,6 @@ int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan 
     pl->Mp = var_rows ? var_rows : (m + TGP_PW - 1) / TGP_PW * TGP_PW;   // 256: the covariance uses the panel layout too
     pl->nPm = (int)(pl->Mp / TGP_PW);
     TGP_ARG(pl->Mp <= 65535 && pl->Mp % TGP_PW == 0);
-    auto rup = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t tail = var_rows ? 2 * rup((size_t)pl->Mp * 8) : rup((size_t)pl->Mp * pl->Mp * 8);
     const size_t need = (coords ? rup(2 * pl->n * 8) + rup(2 * m * 8) : 0) + rup((size_t)pl->Mp * pl->Np * 8) + tail;
     int rc = tgp_ensure_scratch(ctx, need);
@@ -196,6 +182,20 @@ int cov_substitute(tgp_ctx *ctx, tgp_factor *f, const CovPlan &pl, bool tri) {
     TGP_HIP(hipGetLastError());
     return 0;
 }
+// `cols` columns of `rows` rows between a row-major host array (ld `hld`) and 256-wide device panels of Mp rows: one 2D copy per
+// panel, in panel order, on the context's stream
+int copy_panels(tgp_ctx *ctx, hipMemcpyKind kind, const double *host, int64_t hld, int64_t rows, int64_t cols, double *dev,
+                int64_t Mp) {
+    for (int64_t p = 0; p * TGP_PW < cols; ++p) {
+        const size_t w = (size_t)(cols - p * TGP_PW < TGP_PW ? cols - p * TGP_PW : TGP_PW) * 8;
+        double *h = const_cast<double *>(host) + p * TGP_PW, *d = dev + p * Mp * TGP_PW;
+        if (kind == hipMemcpyHostToDevice)
+            TGP_HIP(hipMemcpy2DAsync(d, (size_t)TGP_PW * 8, h, (size_t)hld * 8, w, (size_t)rows, kind, ctx->stream));
+        else
+            TGP_HIP(hipMemcpy2DAsync(h, (size_t)hld * 8, d, (size_t)TGP_PW * 8, w, (size_t)rows, kind, ctx->stream));
+    }
+    return 0;
+}
 // d_Bt holds HT, d_C holds k(X2, X2), both in zero-padded panels: substitution, Kss - Bt Bt^T, result to the host
 int cov_finish(tgp_ctx *ctx, tgp_factor *f, const CovPlan &pl, double *cov) {
     hipStream_t st = ctx->stream;
@@ -205,12 +205,8 @@ int cov_finish(tgp_ctx *ctx, tgp_factor *f, const CovPlan &pl, double *cov) {
     cov_syrk_kernel<<<dim3(mt, mt), 256, 0, st>>>(pl.d_C, pl.d_Bt, pl.Mp, pl.nP);
     TGP_HIP(hipGetLastError());
     TGP_HIP(hipEventRecord(ctx->ev[1], st));
-    for (int p = 0; p < pl.nPm; ++p) {
-        const int64_t w = (pl.m - (int64_t)p * TGP_PW < TGP_PW) ? pl.m - (int64_t)p * TGP_PW : TGP_PW;
-        if (w <= 0) break;
-        TGP_HIP(hipMemcpy2DAsync(cov + (int64_t)p * TGP_PW, (size_t)pl.m * 8, pl.d_C + (int64_t)p * pl.Mp * TGP_PW, (size_t)TGP_PW * 8,
-                                 (size_t)w * 8, (size_t)pl.m, hipMemcpyDeviceToHost, st));
-    }
+    rc = copy_panels(ctx, hipMemcpyDeviceToHost, cov, pl.m, pl.m, pl.m, pl.d_C, pl.Mp);
+    if (rc) return rc;
     TGP_HIP(hipEventRecord(ctx->ev[2], st));
     TGP_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
@@ -254,18 +250,10 @@ extern "C" int tgp_gp_predict_cov_dense(tgp_ctx *ctx, tgp_factor *f, const doubl
     TGP_HIP(hipEventRecord(ctx->ev[0], st));
     TGP_HIP(hipMemsetAsync(pl.d_Bt, 0, (size_t)pl.Mp * pl.Np * 8, st));
     TGP_HIP(hipMemsetAsync(pl.d_C, 0, (size_t)pl.Mp * pl.Mp * 8, st));
-    for (int p = 0; p < pl.nP; ++p) {
-        const int64_t w = (n - (int64_t)p * TGP_PW < TGP_PW) ? n - (int64_t)p * TGP_PW : TGP_PW;
-        if (w <= 0) break;
-        TGP_HIP(hipMemcpy2DAsync(pl.d_Bt + (int64_t)p * pl.Mp * TGP_PW, (size_t)TGP_PW * 8, HT + (int64_t)p * TGP_PW, (size_t)n * 8,
-                                 (size_t)w * 8, (size_t)m, hipMemcpyHostToDevice, st));
-    }
-    for (int p = 0; p < pl.nPm; ++p) {
-        const int64_t w = (m - (int64_t)p * TGP_PW < TGP_PW) ? m - (int64_t)p * TGP_PW : TGP_PW;
-        if (w <= 0) break;
-        TGP_HIP(hipMemcpy2DAsync(pl.d_C + (int64_t)p * pl.Mp * TGP_PW, (size_t)TGP_PW * 8, Kss + (int64_t)p * TGP_PW, (size_t)m * 8,
-                                 (size_t)w * 8, (size_t)m, hipMemcpyHostToDevice, st));
-    }
+    rc = copy_panels(ctx, hipMemcpyHostToDevice, HT, n, m, n, pl.d_Bt, pl.Mp);
+    if (rc) return rc;
+    rc = copy_panels(ctx, hipMemcpyHostToDevice, Kss, m, m, m, pl.d_C, pl.Mp);
+    if (rc) return rc;
     return cov_finish(ctx, f, pl, cov);
 }
 
@@ -277,24 +265,14 @@ extern "C" int tgp_gp_predict_cov_dense(tgp_ctx *ctx, tgp_factor *f, const doubl
 #ifndef TGP_VAR_CHUNK_DEFAULT
 #define TGP_VAR_CHUNK_DEFAULT 16384   // rows per chunk (LAB_NOTES.md: 4096 - 32 768 measured)
 #endif
-#define TGP_VAR_CHUNK_MAX 65280       // largest multiple of 256 that the row grids of cov.hip accept (<= 65 535)
 namespace {
-// one wave per query row: each lane squares 2 + 2 doubles of every 256-wide panel row (two 16-byte loads, 1 KiB contiguous
-// per wave and load), lane partials run over the panels in order, then a fixed xor tree across the wave.  No atomics.
+// one wave per query row (row_sqnorm_wave)
 __global__ __launch_bounds__(256) void var_rows_kernel(const double *__restrict__ Bt, int64_t Mp, int nP, int64_t rows,
                                                        const double *__restrict__ kss, double amp, double *__restrict__ var) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= rows) return;                                       // whole waves leave together
-    const double *row = Bt + i * TGP_PW + 2 * lane;
-    double acc = 0.0;
-#pragma unroll 4
-    for (int p = 0; p < nP; ++p) {
-        const double2 a = *(const double2 *)(row + (int64_t)p * Mp * TGP_PW);
-        const double2 b = *(const double2 *)(row + (int64_t)p * Mp * TGP_PW + 128);
-        acc += (a.x * a.x + a.y * a.y) + (b.x * b.x + b.y * b.y);
-    }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    const double acc = row_sqnorm_wave(Bt, Mp, nP, i);
     if (lane == 0) var[i] = (kss ? kss[i] : amp) - acc;
 }
 
@@ -319,9 +297,10 @@ int var_chunk_rows(tgp_ctx *ctx, const tgp_factor *f, int64_t m, int64_t *Mc) {
 
 // HT of every chunk is written into pl.d_Bt by `fill` (rows r0 .. r0 + rows of the queries, Mp rows of panels, zero padded),
 // the dense route's k(x_i, x_i) into pl.d_kss; then substitution, norms, the chunk's variances to var + r0.
+// `tri` (tgp_factor_inv_diag): the chunk's rows are the identity's from column r0 on, so it stores and sums those panels only.
 // Timings: [3] device compute, [9] transfer of the result, each summed over the chunks.
 template <class Fill>
-int var_chunks(tgp_ctx *ctx, tgp_factor *f, CovPlan &pl, int64_t Mc, double amp, bool dense, double *var, Fill fill) {
+int var_chunks(tgp_ctx *ctx, tgp_factor *f, CovPlan &pl, int64_t Mc, double amp, bool dense, bool tri, double *var, Fill fill) {
     hipStream_t st = ctx->stream;
     double t_dev = 0.0, t_d2h = 0.0;
     for (int64_t r0 = 0; r0 < pl.m; r0 += Mc) {
@@ -329,12 +308,14 @@ int var_chunks(tgp_ctx *ctx, tgp_factor *f, CovPlan &pl, int64_t Mc, double amp,
         CovPlan cp = pl;
         cp.Mp = (rows + TGP_PW - 1) / TGP_PW * TGP_PW;          // a short last chunk substitutes only the rows it has
         cp.nPm = (int)(cp.Mp / TGP_PW);
+        cp.c0 = tri ? r0 : 0;
+        const int np = cp.nP - (int)(cp.c0 >> 8);               // panels the chunk stores
         if (r0 > 0) TGP_HIP(hipEventRecord(ctx->ev[0], st));     // (the first chunk's interval starts before the uploads)
-        int rc = fill(cp, r0, rows);
+        int rc = fill(cp, r0, rows, np);
         if (rc) return rc;
-        rc = cov_substitute(ctx, f, cp, false);
+        rc = cov_substitute(ctx, f, cp, tri);
         if (rc) return rc;
-        var_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(cp.d_Bt, cp.Mp, cp.nP, rows, dense ? cp.d_kss : nullptr, amp, cp.d_v);
+        var_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(cp.d_Bt, cp.Mp, np, rows, dense ? cp.d_kss : nullptr, amp, cp.d_v);
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[1], st));
         TGP_HIP(hipMemcpyAsync(var + r0, cp.d_v, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
@@ -368,7 +349,7 @@ extern "C" int tgp_gp_predict_var(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel 
     TGP_HIP(hipMemcpyAsync(pl.d_X, X, 2 * n * 8, hipMemcpyHostToDevice, st));
     TGP_HIP(hipMemcpyAsync(pl.d_Xs, Xs, 2 * m * 8, hipMemcpyHostToDevice, st));
     // k(x_i, x_i) of the four parametrised kinds is exactly amp (the self kernel's diagonal, tgp_kernel_matrix)
-    return var_chunks(ctx, f, pl, Mc, k->amp, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows) {
+    return var_chunks(ctx, f, pl, Mc, k->amp, false, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows, int) {
         return launch_cross_panels(ctx, k, cp.d_Xs + 2 * r0, rows, cp.d_X, n, 0, cp.d_Bt, cp.Mp, cp.Np);
     });
 }
@@ -386,14 +367,10 @@ extern "C" int tgp_gp_predict_var_dense(tgp_ctx *ctx, tgp_factor *f, const doubl
     if (rc) return rc;
     const int64_t n = f->n;
     TGP_HIP(hipEventRecord(ctx->ev[0], st));
-    return var_chunks(ctx, f, pl, Mc, 0.0, true, var, [&](const CovPlan &cp, int64_t r0, int64_t rows) -> int {
+    return var_chunks(ctx, f, pl, Mc, 0.0, true, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows, int) -> int {
         TGP_HIP(hipMemsetAsync(cp.d_Bt, 0, (size_t)cp.Mp * cp.Np * 8, st));
-        for (int p = 0; p < cp.nP; ++p) {
-            const int64_t w = (n - (int64_t)p * TGP_PW < TGP_PW) ? n - (int64_t)p * TGP_PW : TGP_PW;
-            if (w <= 0) break;
-            TGP_HIP(hipMemcpy2DAsync(cp.d_Bt + (int64_t)p * cp.Mp * TGP_PW, (size_t)TGP_PW * 8, HT + r0 * n + (int64_t)p * TGP_PW,
-                                     (size_t)n * 8, (size_t)w * 8, (size_t)rows, hipMemcpyHostToDevice, st));
-        }
+        int rc = copy_panels(ctx, hipMemcpyHostToDevice, HT + r0 * n, n, rows, n, cp.d_Bt, cp.Mp);
+        if (rc) return rc;
         TGP_HIP(hipMemcpyAsync(cp.d_kss, kss + r0, (size_t)rows * 8, hipMemcpyHostToDevice, st));
         return 0;
     });
@@ -417,7 +394,7 @@ __global__ __launch_bounds__(256) void ident_chunk_kernel(double *Bt, int64_t Mp
     const int64_t li = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (li >= Mp) return;
     const int64_t i = c0 + li;
-    Bt[((i >> 8) - (c0 >> 8)) * Mp * TGP_PW + li * TGP_PW + (i & 255)] = 1.0;
+    Bt[panel_elem(li, i, Mp) - (c0 >> 8) * Mp * TGP_PW] = 1.0;
 }
 
 // rows per chunk: TGP_INVDIAG_CHUNK (rounded up to the step) or the default, at most the largest multiple of the step that the
@@ -459,35 +436,14 @@ extern "C" int tgp_factor_inv_diag(tgp_ctx *ctx, tgp_factor *f, double *d) {
     CovPlan pl;
     rc = cov_plan(ctx, f, n, false, &pl, R < f->Np ? R : f->Np);   // d_Bt: the first chunk, at most Np x Np
     if (rc) return rc;
-    double t_dev = 0.0, t_d2h = 0.0;
-    for (int64_t r0 = 0; r0 < n; r0 += R) {
-        const int64_t rows = (n - r0) < R ? (n - r0) : R;
-        CovPlan cp = pl;
-        cp.Mp = (rows + TGP_PW - 1) / TGP_PW * TGP_PW;          // r0 + Mp <= Np: the chunk's rows are rows of the factor
-        cp.nPm = (int)(cp.Mp / TGP_PW);
-        cp.c0 = r0;
-        const int64_t np = cp.nP - (r0 >> 8);                   // panels the chunk stores
-        if (r0 > 0) TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    // kss = nullptr, amp = 0: var_rows_kernel leaves 0 - |row|^2, negated exactly on the host
+    rc = var_chunks(ctx, f, pl, R, 0.0, false, true, d, [&](const CovPlan &cp, int64_t r0, int64_t, int np) -> int {
         TGP_HIP(hipMemsetAsync(cp.d_Bt, 0, (size_t)cp.Mp * np * TGP_PW * 8, st));
         ident_chunk_kernel<<<(unsigned)(cp.Mp / 256), 256, 0, st>>>(cp.d_Bt, cp.Mp, r0);
-        rc = cov_substitute(ctx, f, cp, true);
-        if (rc) return rc;
-        // kss = nullptr, amp = 0: var_rows_kernel leaves 0 - |row|^2, negated exactly on the host
-        var_rows_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, st>>>(cp.d_Bt, cp.Mp, (int)np, rows, nullptr, 0.0, cp.d_v);
-        TGP_HIP(hipGetLastError());
-        TGP_HIP(hipEventRecord(ctx->ev[1], st));
-        TGP_HIP(hipMemcpyAsync(d + r0, cp.d_v, (size_t)rows * 8, hipMemcpyDeviceToHost, st));
-        TGP_HIP(hipEventRecord(ctx->ev[2], st));
-        TGP_HIP(hipStreamSynchronize(st));
-        float ms = 0.f;
-        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-        t_dev += ms;
-        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
-        t_d2h += ms;
-    }
+        return 0;
+    });
+    if (rc) return rc;
     for (int64_t i = 0; i < n; ++i) d[i] = -d[i];
-    ctx->timings[3] = t_dev;                    // device compute
-    ctx->timings[9] = t_d2h;                    // (n) result to the caller's buffer
     return 0;
 }
 
@@ -501,77 +457,27 @@ extern "C" int tgp_factor_inv_diag(tgp_ctx *ctx, tgp_factor *f, double *d) {
 namespace {
 __global__ __launch_bounds__(256) void ident_panels_kernel(double *Bt, int64_t Mp, int64_t Np) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < Np) Bt[(i >> 8) * Mp * TGP_PW + i * TGP_PW + (i & 255)] = 1.0;
+    if (i < Np) Bt[panel_elem(i, i, Mp)] = 1.0;
 }
 
 // lower tile pairs (ti >= tj), linear in blockIdx.x:  C(ti, tj) = -sum_{p >= ti / 2} Bt[ti][p] Bt[tj][p]^T   (C zero before)
 __global__ __launch_bounds__(256, 2) void kinv_syrk_kernel(double *Cpm, const double *Bt, int64_t Mp, int nP) {
-    const int64_t t = blockIdx.x;
-    int64_t ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > t) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-    const int64_t tj = t - ti * (ti + 1) / 2;
-    const int64_t p0 = ti >> 1;                                     // row tile ti of L^-T is zero left of its own panel
-    const double *a = Bt + p0 * Mp * TGP_PW + ti * TGP_TB * TGP_PW;
-    const double *b = Bt + p0 * Mp * TGP_PW + tj * TGP_TB * TGP_PW;
-    double *c = Cpm + (tj >> 1) * Mp * TGP_PW + ti * TGP_TB * TGP_PW + (tj & 1) * TGP_TB;
-    gemm_tile_dtv<4, TGP_PW, 0>(a, b, c, nullptr, nullptr, nP - (int)p0, Mp * TGP_PW, Mp * TGP_PW);
+    int64_t ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    post_syrk_tile(Cpm, Bt, Mp, nP, ti, tj, ti >> 1);               // row tile ti of L^-T is zero left of its own panel
 }
 
 // 64 rows x one 256-column panel per workgroup over the lower triangle; four partial sums per workgroup
 __global__ __launch_bounds__(256) void loglik_grad_kernel(KParams p, const double *__restrict__ X, const double *__restrict__ alpha,
                                                           const double *__restrict__ Cpm, int64_t Mp, int64_t n,
                                                           double *__restrict__ partial) {
-    __shared__ double red[4][4];
-    const int tid = threadIdx.x;
-    const int64_t j = (int64_t)blockIdx.x * TGP_PW + tid;
-    const int64_t i0 = (int64_t)blockIdx.y * 64;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    if ((int64_t)blockIdx.x * TGP_PW <= i0 + 63 && j < n) {
-        const double xj = X[2 * j], yj = X[2 * j + 1], aj = alpha[j];
-        const double *col = Cpm + (int64_t)blockIdx.x * Mp * TGP_PW + tid;
-        for (int r = 0; r < 64; ++r) {
-            const int64_t i = i0 + r;
-            if (i >= n) break;
-            if (j > i) continue;
-            const double m = alpha[i] * aj + col[i * TGP_PW];       // alpha_i alpha_j - [K^-1]_ij   (C holds -K^-1)
-            if (i == j) {
-                acc[0] += 0.5 * m * p.amp;                          // the pair (i, i) counts once, d K_ii / d log amp = amp
-            } else {
-                const double dx = X[2 * i] - xj, dy = X[2 * i + 1] - yj;
-                const double e = p.amp * exp(-0.5 * quad_form(p, dx, dy)) * m;
-                acc[0] += e;
-                acc[1] -= 0.5 * e * dx * dx;
-                acc[2] -= e * dx * dy;
-                acc[3] -= 0.5 * e * dy * dy;
-            }
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        double v = acc[q];
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        if ((tid & 63) == 0) red[tid >> 6][q] = v;
-    }
-    __syncthreads();
-    if (tid < 4) partial[((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    loglik_grad_block(p, X, alpha, Cpm, Mp, n, blockIdx.x, (int64_t)blockIdx.y * 64,
+                      partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
 }
 
 // fixed-order sum of the workgroups' partial sums (one workgroup: the result does not depend on the schedule)
 __global__ __launch_bounds__(256) void loglik_grad_reduce_kernel(const double *__restrict__ partial, int64_t count, double *__restrict__ out) {
-    __shared__ double red[256][4];
-    const int tid = threadIdx.x;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t q = tid; q < count; q += 256)
-        for (int s = 0; s < 4; ++s) acc[s] += partial[q * 4 + s];
-    for (int s = 0; s < 4; ++s) red[tid][s] = acc[s];
-    __syncthreads();
-    for (int step = 128; step > 0; step >>= 1) {
-        if (tid < step)
-            for (int s = 0; s < 4; ++s) red[tid][s] += red[tid + step][s];
-        __syncthreads();
-    }
-    if (tid < 4) out[tid] = red[0][tid];
+    loglik_grad_reduce(partial, count, 1, 1, out);          // the partial sums are dense: one run of `count`, read in order
 }
 }  // namespace
 

@@ -12,11 +12,8 @@ __global__ __launch_bounds__(256) void kbuild_lower_kernel(KParams p, const doub
                                                            int64_t Np, const double *__restrict__ yerr,
                                                            double *__restrict__ A) {
     // triangular tile enumeration: b -> (ti, tj), tj <= ti
-    const int64_t b = blockIdx.x;
-    int64_t ti = (int64_t)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-    while (ti * (ti + 1) / 2 > b) --ti;
-    while ((ti + 1) * (ti + 2) / 2 <= b) ++ti;
-    const int64_t tj = b - ti * (ti + 1) / 2;
+    int64_t ti, tj;
+    tri_index(blockIdx.x, ti, tj);
     const int64_t pj = tj >> 1;
     double *tile = A + panel_off(pj, Np) + (ti * TGP_TB - pj * TGP_PW) * TGP_PW + (tj & 1) * TGP_TB;
     kbuild_tile<KE>(p, X, n, yerr, ti, tj, tile);

@@ -25,6 +25,7 @@
 #define TGP_PSYNC_PANELS 1024 // panels with a counter set of their own (Np <= 262144); 16 words = 64 B each
 #define TGP_TB 128            // tile / diagonal-block size
 #define TGP_PW 256            // panel width = trailing-update depth
+#define TGP_VAR_CHUNK_MAX 65280   // most query rows per launch: the largest multiple of 256 that a row grid accepts (<= 65 535)
 
 struct tgp_ctx {
     int device = 0;
@@ -99,6 +100,15 @@ __host__ __device__ inline int64_t panel_off(int64_t p, int64_t Np) {
 __host__ __device__ inline int64_t padded_n(int64_t n) {
     return (n + TGP_PW - 1) / TGP_PW * TGP_PW;
 }
+// bytes rounded up to the 256-byte granule of the scratch arenas
+inline size_t rup(size_t b) { return (b + 255) / 256 * 256; }
+// row-major enumeration of a lower triangle: t -> (ti, tj), tj <= ti, t = ti (ti + 1) / 2 + tj
+__host__ __device__ inline void tri_index(int64_t t, int64_t &ti, int64_t &tj) {
+    ti = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (ti * (ti + 1) / 2 > t) --ti;
+    while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+    tj = t - ti * (ti + 1) / 2;
+}
 
 // ---- multi-GPU row-block-cyclic geometry (blocks of 256 rows) ----
 // The owner map is the block-cyclic deal REFLECTED every G blocks ("snake"): round q = b / G hands one block to every rank,
@@ -172,10 +182,8 @@ __host__ __device__ inline void tilemap(int64_t b, int64_t T, int &ti, int &tj) 
         if (st >= ns || within >= per) return;
     }
     // st -> (Si, Sj), Sj <= Si, row-major triangular enumeration
-    int64_t Si = (int64_t)((sqrt(8.0 * (double)st + 1.0) - 1.0) * 0.5);
-    while (Si * (Si + 1) / 2 > st) --Si;
-    while ((Si + 1) * (Si + 2) / 2 <= st) ++Si;
-    const int64_t Sj = st - Si * (Si + 1) / 2;
+    int64_t Si, Sj;
+    tri_index(st, Si, Sj);
     const int i = (int)((Si << sh) + (within >> sh));
     const int j = (int)((Sj << sh) + (within & ((1 << sh) - 1)));
     if (j > i || i >= T) return;
