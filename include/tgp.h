@@ -8,6 +8,7 @@
  *   S2  cholesky + cho_solve (+ logdet)  treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33
  *   S2e many small S2 at once           treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33, 43-62, README.rst:28
  *   S2f many small S2 + S2d at once     treegp/log_likelihood.py:43-62 for the problems of S2e (one evaluation of many fits)
+ *   S2g many small S2 + diag(K^-1)      not in the reference: leave-one-out for the problems of S2e (R&W 5.4.2)
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
@@ -162,6 +163,24 @@ int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t
 int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
                             const double *X, const double *y, const double *yerr,
                             double *logdet, double *ydota, double *grad, int32_t *info);
+
+/* ---- S2g: S2 and diag(K^-1) for the nb problems of S2e, in the same call ------------------------------------------------------
+ * Between fitting and interpolating, a pipeline with one GP per PSF parameter, exposure or chip (README.rst:28) validates each
+ * fit and rejects outliers by leave-one-out (Rasmussen & Williams 5.4.2; not in the reference): that needs alpha and the
+ * diagonal of the inverse alone, S3e for one kept factor at a time.  Here the batch of S2e is factorised and solved as
+ * tgp_gp_solve_batch does it and, in the same chunk, each problem's factor gives
+ *   invdiag[b][i] = [(K_b + diag(yerr_b^2))^-1]_ii = |L_b^-1 e_i|^2   for i < ns[b], exactly 0 for ns[b] <= i < nmax
+ * from L_b^-T substituted on the device as in S2f, without its K^-1 (half of its flops behind the solve).  invdiag is
+ * (nb, nmax) and must not be NULL.  ks, ns, nmax, X, y, yerr, alpha (may be NULL), logdet, ydota (may be NULL) and info as
+ * tgp_gp_solve_batch, bit for bit; all four kernel kinds; a problem with info[b] > 0 has meaningless outputs and the others are
+ * unaffected, bit for bit.  A problem's bits depend neither on its companions, nor on its place in the batch, nor on nmax, nor
+ * on the chunking (TGP_BATCH_CHUNK, as S2e; the chunk also holds L^-T, Np x Np, and nmax doubles per problem).
+ * Returns 0 when every problem was attempted; -1 for the argument errors of S2e or a NULL invdiag; -2 for HIP errors.
+ * Timings [0] K build, [1] Cholesky, [2] sweeps and logdet, [3] substitution and norms, summed over the chunks; every other
+ * slot 0.                                                                                                                      */
+int tgp_gp_loo_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+                     const double *X, const double *y, const double *yerr,
+                     double *alpha, double *invdiag, double *logdet, double *ydota, int32_t *info);
 
 /* ---- S3: ys[j] = sum_i amp k(Xs_j, X_i) alpha_i, HT never materialised -------------------*/
 int tgp_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n,

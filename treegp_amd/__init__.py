@@ -8,7 +8,7 @@ of ``include/tgp.h``; importing the package needs no GPU, computing does.
 __version__ = "0.1.0"
 __version_info__ = tuple(map(int, __version__.split(".")))
 
-from .gp_interp import GPInterpolation, predict_many
+from .gp_interp import GPInterpolation, predict_many, predict_loo_many, loo_log_predictive_many
 from .kernels import AnisotropicRBF, VonKarman, AnisotropicVonKarman, eval_kernel, kernel_to_spec
 from .two_pcf import two_pcf  # noqa: F401  (class shadows the module, as in the reference)
 from .log_likelihood import log_likelihood  # noqa: F401
@@ -19,4 +19,4 @@ from .fit_many import solve_many
 
 __all__ = ["__version__", "__version_info__", "GPInterpolation", "two_pcf", "log_likelihood", "AnisotropicRBF",
            "VonKarman", "AnisotropicVonKarman", "eval_kernel", "kernel_to_spec", "meanify", "comp_eb", "comp_eb_treecorr",
-           "gaussian_random_field", "predict_many", "solve_many"]
+           "gaussian_random_field", "predict_many", "solve_many", "predict_loo_many", "loo_log_predictive_many"]

@@ -73,6 +73,7 @@ SIGNATURES = {
     "tgp_factor_inv_diag": (C.c_int, [_vp, _vp, _vp]),
     "tgp_gp_solve_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_solve_grad_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tgp_gp_loo_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_posterior_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_predict_cov_dense": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp]),
     "tgp_gp_predict_var": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _i64, _vp]),

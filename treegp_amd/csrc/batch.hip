@@ -360,6 +360,43 @@ __global__ __launch_bounds__(256) void bloglik_grad_reduce_kernel(const double *
     loglik_grad_reduce(partial + (int64_t)b * g.nrb * g.nP * 4, (n + 63) / 64, (n + TGP_PW - 1) / TGP_PW, g.nP, out + (int64_t)b * 4);
 }
 
+// ---- diag(K^-1) of every problem (seam S2g): the substitution of S2f without its C_b ---------------------------------------------
+// Bt_b = L_b^-T as above (Np x Np panels at b * Np * Np, the same init region, the same substitution launches); row i of it is
+// L_b^-1 e_i, so [K_b^-1]_ii is its squared norm, taken from the row's own panel (i / 128) / 2 on: nothing left of the
+// initialised region is read.  The panels behind n_b hold exact zeros in the rows below n_b and come last in the sum, so a larger
+// Np changes no bit.
+
+// Bt_b <- identity where the substitution reads it: row tile ti = blockIdx.x / nP below n_b, panel p = blockIdx.x % nP from ti / 2 on
+__global__ __launch_bounds__(256) void binv_init_kernel(double *__restrict__ Bt, const int64_t *__restrict__ ns, int64_t Np, int nP) {
+    const int b = blockIdx.y;
+    const int64_t ti = blockIdx.x / nP, p = blockIdx.x % nP;
+    if (ti * TGP_TB >= ns[b] || p < (ti >> 1)) return;
+    const int64_t base = (int64_t)b * Np * Np + p * Np * TGP_PW + ti * TGP_TB * TGP_PW;
+    const int r0 = threadIdx.x >> 7, c = 2 * (threadIdx.x & 127);
+    for (int r = r0; r < TGP_TB; r += 2) {
+        const int64_t i = ti * TGP_TB + r, j = p * TGP_PW + c;
+        double2 v = {j == i ? 1.0 : 0.0, j + 1 == i ? 1.0 : 0.0};
+        *reinterpret_cast<double2 *>(Bt + base + (int64_t)r * TGP_PW + c) = v;
+    }
+}
+
+// invdiag_b[i] = |Bt_b[i, :]|^2 over the panels (i / 128) / 2 .. Np / 256 - 1, one wave per row (row_sqnorm_wave_from); rows
+// >= n_b of the caller's (nb, nmax) layout are exactly 0
+__global__ __launch_bounds__(256) void binv_diag_kernel(const double *__restrict__ Bt, const int64_t *__restrict__ ns, int64_t Np,
+                                                        int64_t nmax, double *__restrict__ invdiag) {
+    const int b = blockIdx.y;
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nmax) return;                                       // whole waves leave together
+    double *out = invdiag + (int64_t)b * nmax + i;
+    if (i >= ns[b]) {
+        if (lane == 0) *out = 0.0;
+        return;
+    }
+    const double acc = row_sqnorm_wave_from(Bt + (int64_t)b * Np * Np, Np, (int)(Np / TGP_PW), i, (int)((i / TGP_TB) >> 1));
+    if (lane == 0) *out = acc;
+}
+
 }  // namespace
 
 // problems per chunk: TGP_BATCH_CHUNK, or as many as 90 % of the free device memory holds (the context's own scratch counted as
@@ -741,6 +778,20 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
     return 0;
 }
 
+// Bt_b <- L_b^-T for the `ncn` problems of a chunk, Bt_b holding the identity (S2f and S2g): the block substitution over the
+// 128-column blocks kb; at step kb only the row tiles ti <= kb hold anything.  Bt_b is square: the "query rows" are the
+// problem's own, ms = ns.
+static void batch_subst_identity(hipStream_t st, double *dBt, const BatchBufs &bb, const BatchDims &d, unsigned ncn) {
+    const int nT = (int)(d.Np / TGP_TB);
+    const PostDims q{d.Np, 0};                                    // (mmax is not read by the substitution)
+    for (int kb = 0; kb < nT; ++kb) {
+        const int live = kb + 1;
+        btrsm_kernel<<<dim3((unsigned)live, ncn), 256, 0, st>>>(dBt, bb.dW, bb.dns, bb.dns, d, q, kb);
+        const int nc = nT - kb - 1;
+        if (nc > 0) bupdate_kernel<<<dim3((unsigned)(live * nc), ncn), 256, 0, st>>>(dBt, bb.dA, bb.dns, bb.dns, d, q, kb, live);
+    }
+}
+
 // ---- S2f: the likelihood gradient of every problem of S2e from its factor and alpha, in the same call ---------------------------
 // Per chunk, after batch_factor_chunk with both sweeps: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row
 // tiles, C_b = -Bt_b Bt_b^T over the lower tile pairs, the reduction against dK/dp and one fixed-order sum per problem.
@@ -765,7 +816,6 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
     hipStream_t st = ctx->stream;
     const BatchDims &d = r.d;
     const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
-    const PostDims q{Np, nmax};                                   // Bt_b is square: the "query rows" are the problem's own
     const GradDims g{Np / 64, nP};
     // per problem beside S2e's arrays: Bt and C (Np x Np each), the reduction's partial sums, the four results
     rc = batch_arena(r, 2 * rup((size_t)Np * Np * 8) + rup((size_t)(g.nrb * g.nP) * 32) + rup(32));
@@ -784,19 +834,57 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
         if (rc) return rc;
         TGP_HIP(hipEventRecord(ctx->ev[4], st));
         bgrad_init_kernel<<<dim3((unsigned)(nT * nP), ncn), 256, 0, st>>>(dBt, dC, bb.dns, Np, (int)nP);
-        // Bt_b <- L_b^-T: at step kb only the row tiles ti <= kb hold anything
-        for (int kb = 0; kb < (int)nT; ++kb) {
-            const int live = kb + 1;
-            btrsm_kernel<<<dim3((unsigned)live, ncn), 256, 0, st>>>(dBt, bb.dW, bb.dns, bb.dns, d, q, kb);
-            const int nc = (int)nT - kb - 1;
-            if (nc > 0) bupdate_kernel<<<dim3((unsigned)(live * nc), ncn), 256, 0, st>>>(dBt, bb.dA, bb.dns, bb.dns, d, q, kb, live);
-        }
+        batch_subst_identity(st, dBt, bb, d, ncn);
         bkinv_syrk_kernel<<<dim3((unsigned)(nT * (nT + 1) / 2), ncn), 256, 0, st>>>(dC, dBt, bb.dns, Np, (int)nP);
         bloglik_grad_kernel<<<dim3((unsigned)(g.nrb * g.nP), ncn), 256, 0, st>>>(bb.dkp, bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
         bloglik_grad_reduce_kernel<<<ncn, 256, 0, st>>>(dpart, bb.dns, g, dgrad);
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[5], st));
         rc = batch_end_chunk(r, c0, cn, grad + c0 * 4, dgrad, (size_t)cn * 32, 1);
+        if (rc) return rc;
+    }
+    batch_finish(r);
+    return 0;
+}
+
+// ---- S2g: diag(K^-1) of every problem of S2e from its factor, in the same call (leave-one-out, R&W 5.4.2) ----------------------
+// Per chunk, after batch_factor_chunk: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row tiles (the
+// launches of S2f), then one wave per row for |row i of Bt_b|^2 from the row's own panel on.  No C_b: half of S2f's flops behind
+// the solve, one Np x Np buffer per problem.
+int tgp_gp_loo_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X, const double *y,
+                     const double *yerr, double *alpha, double *invdiag, double *logdet, double *ydota, int32_t *info) {
+    static const char *fn = "tgp_gp_loo_batch";
+    if (!ctx) return -1;
+    if (!(ks && ns && X && y && invdiag && logdet && info)) {
+        ctx->err = "tgp_gp_loo_batch: ks, ns, X, y, invdiag, logdet and info must not be NULL";
+        return -1;
+    }
+    BatchRun r;
+    int rc = batch_begin(r, ctx, fn, nb, ks, ns, nmax, alpha, logdet, ydota, info);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const BatchDims &d = r.d;
+    const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
+    // per problem beside S2e's arrays: Bt (Np x Np) and the diagonal in the caller's layout
+    rc = batch_arena(r, rup((size_t)Np * Np * 8) + rup((size_t)nmax * 8));
+    if (rc) return rc;
+    const int64_t C = r.C;
+    BatchBufs &bb = r.bb;
+    double *dBt = (double *)r.take((size_t)C * Np * Np * 8);
+    double *dD = (double *)r.take((size_t)C * nmax * 8);
+
+    for (int64_t c0 = 0; c0 < nb; c0 += C) {
+        const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
+        const unsigned ncn = (unsigned)cn;
+        rc = batch_factor_chunk(ctx, d, bb, c0, cn, ks, ns, nmax, X, y, yerr, alpha != nullptr);
+        if (rc) return rc;
+        TGP_HIP(hipEventRecord(ctx->ev[4], st));
+        binv_init_kernel<<<dim3((unsigned)(nT * nP), ncn), 256, 0, st>>>(dBt, bb.dns, Np, (int)nP);
+        batch_subst_identity(st, dBt, bb, d, ncn);
+        binv_diag_kernel<<<dim3((unsigned)((nmax + 3) / 4), ncn), 256, 0, st>>>(dBt, bb.dns, Np, nmax, dD);
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipEventRecord(ctx->ev[5], st));
+        rc = batch_end_chunk(r, c0, cn, invdiag + c0 * nmax, dD, (size_t)cn * nmax * 8, 1);
         if (rc) return rc;
     }
     batch_finish(r);

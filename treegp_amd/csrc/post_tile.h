@@ -63,6 +63,24 @@ __device__ __forceinline__ double row_sqnorm_wave(const double *__restrict__ Bt,
     return acc;
 }
 
+// The same over the panels p0 .. nP - 1 only, for a row that is zero (or was never written) left of panel p0: row i of
+// Bt = L^-T with p0 = (i / 128) / 2, whose squared norm is [K^-1]_ii.  Same loads and the same order (panels in order from p0,
+// then the xor tree); the products are spelled out as fma so that every trip of the loop, unrolled or not, rounds alike:
+// trailing panels of exact zeros add nothing, whatever nP is.  No atomics.  Every lane returns the sum.
+__device__ __forceinline__ double row_sqnorm_wave_from(const double *__restrict__ Bt, int64_t Mp, int nP, int64_t i, int p0) {
+    const int lane = threadIdx.x & 63;
+    const double *row = Bt + i * TGP_PW + 2 * lane;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int p = p0; p < nP; ++p) {
+        const double2 a = *(const double2 *)(row + (int64_t)p * Mp * TGP_PW);
+        const double2 b = *(const double2 *)(row + (int64_t)p * Mp * TGP_PW + 128);
+        acc += fma(a.y, a.y, a.x * a.x) + fma(b.y, b.y, b.x * b.x);
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    return acc;
+}
+
 // The likelihood gradient's pair sum of one workgroup: rows i0 .. i0 + 63 x the 256-column panel pj of the lower triangle
 // below n, against C = -K^-1 (panels of Mp rows); the four partial sums to out[0 .. 3]
 __device__ __forceinline__ void loglik_grad_block(const KParams &p, const double *__restrict__ X, const double *__restrict__ alpha,

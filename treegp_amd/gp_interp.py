@@ -443,13 +443,13 @@ def predict_many(gps, Xs, return_cov=False, return_var=False):
     return [gp.predict(X) for gp, X in zip(gps, Xs)]
 
 
-def _batch_spec(gp):
-    """the device kernel of an object the batched routes may take (kernel_to_spec describes it, not on the multi-GPU
-    route, at most 4096 points), else None"""
+def _batch_spec(gp, kernel=None):
+    """the device kernel of an object the batched routes may take (kernel_to_spec describes it -- ``gp.kernel``, or the given
+    one -- not on the multi-GPU route, at most 4096 points), else None"""
     if gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX:
         return None
     try:
-        spec = kernel_to_spec(gp.kernel)
+        spec = kernel_to_spec(gp.kernel if kernel is None else kernel)
     except NotImplementedError:
         return None
     with gp._scope():
@@ -458,11 +458,11 @@ def _batch_spec(gp):
     return spec
 
 
-def _raise_failed(picked, info):
+def _raise_failed(picked, info, who="predict_many"):
     for j, i in enumerate(picked):
         if info[j] > 0:
-            raise np.linalg.LinAlgError("predict_many: GP %d: %d-th leading minor of the array is not positive definite"
-                                        % (i, info[j]))
+            raise np.linalg.LinAlgError("%s: GP %d: %d-th leading minor of the array is not positive definite"
+                                        % (who, i, info[j]))
 
 
 def _predict_many_posterior(gps, Xs, what):
@@ -495,4 +495,85 @@ def _predict_many_posterior(gps, Xs, what):
             out.append((gp.predict(X), uncs[i]))
         else:
             out.append(gp.predict(X, return_cov=what == "cov", return_var=what == "var"))
+    return out
+
+
+def predict_loo_many(gps, return_var=False):
+    """``[gp.predict_loo(return_var) for gp in gps]`` with the factorisations and diag(K^-1) of many small GPs in one batched
+    call (ops.gp_loo_batch): the validation step between ``solve_many`` and ``predict_many``.  The objects the batched routes
+    take (``kernel_to_spec`` describes the kernel, not on the multi-GPU route, at most 4096 points) and that hold no kept factor
+    of the same data go through it, then through ``loo_quantities`` on the host exactly as ``predict_loo``; a cached alpha is
+    kept, an object without one caches the batch's, and no kept factor is left behind.  Every other object goes through its own
+    ``predict_loo``.  A failed factorisation raises numpy.linalg.LinAlgError naming the object's index (nothing is cached
+    then)."""
+    gps = list(gps)
+    picked, specs = [], []
+    for i, gp in enumerate(gps):
+        spec = _batch_spec(gp)
+        if spec is None:
+            continue
+        if gp._factor is not None and gp._factor_key == gp._factor_fingerprint(spec, gp._X, gp._y_err):
+            continue                              # its own predict_loo reuses the kept factor: no factorisation to save
+        picked.append(i)
+        specs.append(spec)
+    done = {}
+    if picked:
+        residuals = [gps[i]._residual() for i in picked]
+        alphas, ds, _, _, info = ops.gp_loo_batch(specs, [gps[i]._X for i in picked], residuals,
+                                                  [gps[i]._y_err for i in picked])
+        _raise_failed(picked, info, "predict_loo_many")
+        for j, i in enumerate(picked):
+            gp = gps[i]
+            if gp._alpha is None:
+                gp._alpha = alphas[j]             # a cached alpha stays, as in _ensure_solution
+            gp._set_factor(None, None)
+            mu, _, v, _ = loo_quantities(residuals[j], gp._alpha, ds[j], gp._y_err)
+            y_loo = mu + gp._mean + gp._spatial_average
+            done[i] = (y_loo, v) if return_var else y_loo
+    return [done[i] if i in done else gp.predict_loo(return_var=return_var) for i, gp in enumerate(gps)]
+
+
+def loo_log_predictive_many(gps, thetas=None):
+    """``[gp.return_loo_log_predictive(theta) for gp, theta in zip(gps, thetas)]`` as a float array, the objects the batched
+    routes take in one batched call (ops.gp_loo_batch).  ``thetas``: None, or a list with None or a theta per object, cloned
+    into a copy of the object's kernel.  -inf for a factorisation that fails or a sum that is not finite, as the single method;
+    ``_alpha``, the kept factor and ``gp.kernel`` of every object are left untouched.  Every other object goes through its own
+    ``return_loo_log_predictive``."""
+    from ._lib import TgpError
+    gps = list(gps)
+    thetas = [None] * len(gps) if thetas is None else list(thetas)
+    if len(thetas) != len(gps):
+        raise ValueError("loo_log_predictive_many: %d GPs but %d thetas" % (len(gps), len(thetas)))
+    out = np.full(len(gps), -np.inf)
+    picked, specs = [], []
+    for i, (gp, theta) in enumerate(zip(gps, thetas)):
+        kernel = copy.deepcopy(gp.kernel)
+        if theta is not None:
+            kernel = kernel.clone_with_theta(theta)
+        spec = _batch_spec(gp, kernel)
+        if spec is None:
+            out[i] = gp.return_loo_log_predictive(theta)
+        else:
+            picked.append(i)
+            specs.append(spec)
+    if picked:
+        residuals = [gps[i]._residual() for i in picked]
+        try:
+            alphas, ds, _, _, info = ops.gp_loo_batch(specs, [gps[i]._X for i in picked], residuals,
+                                                      [gps[i]._y_err for i in picked])
+        except TgpError as ex:
+            # judged as a device error of one evaluation (log_likelihood._rejects_theta): an argument error, or any error
+            # under TGP_ML_STRICT=1, raises; a run-time one warns, and every object meets what its own method gives it
+            from .log_likelihood import _rejects_theta
+            if not _rejects_theta(ex):
+                raise
+            for i in picked:
+                out[i] = gps[i].return_loo_log_predictive(thetas[i])
+            return out
+        for j, i in enumerate(picked):
+            if info[j] > 0:
+                continue
+            with np.errstate(invalid="ignore", divide="ignore"):
+                total = float(np.sum(loo_quantities(residuals[j], alphas[j], ds[j], gps[i]._y_err)[3]))
+            out[i] = total if np.isfinite(total) else -np.inf
     return out

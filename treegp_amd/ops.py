@@ -206,6 +206,36 @@ def gp_solve_grad_batch(specs, Xs, ys, y_errs=None, ctx=None):
     return logdet, chi2, g4, info.astype(np.int64)
 
 
+def gp_loo_batch(specs, Xs, ys, y_errs=None, ctx=None):
+    """gp_solve_batch plus, from each problem's factor in the same call, d_b = diag((K_b + diag(y_err_b^2))^-1)
+    (tgp_gp_loo_batch): with alpha, all that the leave-one-out quantities of a GP need (treegp_amd.loo).  Arguments as
+    gp_solve_batch; every kernel kind.  Returns (alphas, invdiags: lists of (n_b,) arrays, logdets (nb,), chi2 = y.alpha (nb,),
+    info (nb,) int): alphas, logdets, chi2 and info are bit for bit gp_solve_batch's, info[b] > 0 marks a problem whose other
+    outputs are meaningless, and each problem's result does not depend on the others in the call."""
+    specs = list(specs)
+    ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("gp_loo_batch: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("gp_loo_batch: problems of order up to %d, got %d (use gp_solve and factor_inv_diag)"
+                         % (BATCH_NMAX, nmax))
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    alpha = np.empty((nb, nmax))
+    invdiag = np.empty((nb, nmax))
+    logdet = np.empty(nb)
+    chi2 = np.empty(nb)
+    info = np.zeros(nb, dtype=np.int32)
+    rc = lib.tgp_gp_loo_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(alpha),
+                              ptr(invdiag), ptr(logdet), ptr(chi2), ptr(info))
+    check(ctx, rc, "tgp_gp_loo_batch")
+    alphas = [alpha[b, :int(ns[b])].copy() for b in range(nb)]
+    invdiags = [invdiag[b, :int(ns[b])].copy() for b in range(nb)]
+    return alphas, invdiags, logdet, chi2, info.astype(np.int64)
+
+
 POSTERIOR_MMAX = {"var": 65280, "cov": 4096}    # tgp_gp_posterior_batch: query points per problem (the row grids of S3b / S3c)
 
 
