@@ -14,6 +14,7 @@
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
  *   S3d realisations y = L z             np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66, 95-97
  *   S3e diag(K^-1) of a kept factor      not in the reference: leave-one-out residuals and variances (R&W 5.4.2)
+ *   S3g gradient of HT @ alpha           not in the reference: d/dX2 of treegp/gp_interp.py:177,183 (kernels.py:114-126, 249-276, 355-381)
  *   S3f many small S3b / S3c at once    treegp/gp_interp.py:184-192 for the problems of S2e, README.rst:28
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
@@ -186,6 +187,23 @@ int tgp_gp_loo_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *
 int tgp_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n,
                    const double *alpha, const double *Xs, int64_t m, double *ys);
 
+/* ---- S3g: gs[j] = sum_i alpha_i amp grad k(x - X_i) at x = Xs_j: the spatial derivative of S3 ---------------------------
+ * Not in the reference, whose users difference predict() at shifted points.  The interpolated fields are PSF parameters and
+ * astrometric displacements over a focal plane: divergence and curl of a displacement field (the map-level counterpart of the
+ * E/B split of S7), local plate scale and shear, the slope of a PSF parameter across a chip.  gs is (m, 2) row-major.  With
+ * (dx, dy) = Xs_j - X_i, q = a dx^2 + 2 b dx dy + c dy^2 and u = sqrt(q), a pair contributes
+ *   Gaussian kinds    -alpha_i amp exp(-q / 2) (a dx + b dy, b dx + c dy)
+ *   TGP_AVK           -alpha_i amp w(u) (a dx + b dy, b dx + c dy),  w(u) = -f'(u) / u = 2 pi u^(-1/6) K_{1/6}(2 pi u) / lim0
+ *   TGP_VK            the same with a = c = 1 / ell^2, b = 0
+ * and exactly 0 when u == 0: the von Karman profile has a cusp at the origin (1 - D u^(5/3)), the field has zero slope on a
+ * star, and differencing predict() across one is wrong by more than rounding.  A 1-D problem (zero second column, b = c = 0,
+ * or TGP_VK) gets a zero second column back.  Same decomposition as S3 (no (m, n) matrix, no atomics): the result is
+ * bit-identical from run to run, and a query's two numbers depend on the training set and its own coordinates only -- not on
+ * m, nor on its place among the queries.  Returns -1 for an unknown kind or n, m < 1, -2 for HIP errors; timings[3] is the
+ * device time.                                                                                                             */
+int tgp_gp_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n,
+                        const double *alpha, const double *Xs, int64_t m, double *gs);
+
 /* ---- S3b: cov (m, m) = k(Xs,Xs) - HT K^-1 HT^T using a kept factor ------------------------*/
 int tgp_gp_predict_cov(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X,
                        int64_t n, const double *Xs, int64_t m, double *cov);
@@ -321,6 +339,8 @@ int tgp_d_gp_solve(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t
                    double *ydota, tgp_factor **keep);
 int tgp_d_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n,
                      const double *d_alpha, const double *d_Xs, int64_t m, double *d_ys);
+int tgp_d_gp_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n,
+                          const double *d_alpha, const double *d_Xs, int64_t m, double *d_gs /* (m, 2) */);
 /* d_K: dense (n, n) row-major on the device (lower triangle read) */
 int tgp_d_gp_solve_dense(tgp_ctx *ctx, const double *d_K, int64_t n, const double *d_y,
                          const double *d_yerr, double *d_alpha, double *logdet, double *ydota,

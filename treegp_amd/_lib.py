@@ -42,6 +42,7 @@ SIGNATURES = {
     "tgp_factor_release": (None, [_vp, _vp]),
     "tgp_factor_borrow": (C.c_int, [_vp, _vp, _vp, _i64, C.POINTER(_vp)]),
     "tgp_gp_predict": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tgp_gp_predict_grad": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _i64, _vp]),
     "tgp_gp_predict_cov": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _i64, _vp]),
     "tgp_kk_twod": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
     "tgp_kk_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
@@ -59,6 +60,7 @@ SIGNATURES = {
     "tgp_mem_info": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "tgp_d_gp_solve": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _vp, _dp, _dp, C.POINTER(_vp)]),
     "tgp_d_gp_predict": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tgp_d_gp_predict_grad": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _i64, _vp]),
     "tgp_panel_off": (_i64, [_i64, _i64]),
     "tgp_panel_elems": (_i64, [_i64]),
     "tgp_padded_n": (_i64, [_i64]),

@@ -810,6 +810,44 @@ int tgp_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n
     return 0;
 }
 
+// ---- S3g --------------------------------------------------------------------------------------
+int tgp_d_gp_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
+                          const double *d_Xs, int64_t m, double *d_gs) {
+    TGP_ARG(k && d_X && d_alpha && d_Xs && d_gs);
+    TGP_HIP(hipSetDevice(ctx->device));
+    TGP_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    int rc = launch_predict_grad(ctx, k, d_X, n, d_alpha, d_Xs, m, d_gs);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+    TGP_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->timings[3] = ms;
+    return 0;
+}
+
+int tgp_gp_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n, const double *alpha,
+                        const double *Xs, int64_t m, double *gs) {
+    TGP_ARG(k && X && alpha && Xs && gs);
+    TGP_ARG(n > 0 && m > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    const size_t io_bytes = rup(2 * n * 8) + rup(n * 8) + 2 * rup(2 * m * 8);
+    int rc = ensure_io(ctx, io_bytes);
+    if (rc) return rc;
+    rc = ensure_hio(ctx, io_bytes);
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_X = ar.take<double>(2 * n), *d_a = ar.take<double>(n), *d_Xs = ar.take<double>(2 * m),
+           *d_gs = ar.take<double>(2 * m);
+    TGP_HIP(h2d(ctx, d_X, X, 2 * n * 8));
+    TGP_HIP(h2d(ctx, d_a, alpha, n * 8));
+    TGP_HIP(h2d(ctx, d_Xs, Xs, 2 * m * 8));
+    rc = tgp_d_gp_predict_grad(ctx, k, d_X, n, d_a, d_Xs, m, d_gs);
+    if (rc) return rc;
+    TGP_HIP(d2h_sync(ctx, gs, d_gs, 2 * m * 8));
+    return 0;
+}
+
 // ---- S1 ---------------------------------------------------------------------------------------
 int tgp_kernel_matrix(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n, const double *Y, int64_t m,
                       double *out) {

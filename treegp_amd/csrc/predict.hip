@@ -9,6 +9,7 @@
 // by a second kernel (bitwise reproducible, no atomics).
 #include "tgp_internal.h"
 #include "kernel_eval.h"
+#include "bessel_k16.h"
 
 namespace {
 constexpr int PT = 256;   // training points per LDS tile
@@ -250,6 +251,115 @@ __global__ __launch_bounds__(256) void predict_reduce_kernel(const double *__res
     for (int k = 0; k < nsplit; ++k) s += partial[(int64_t)k * m + q];
     ys[q] = scale * s;
 }
+// ---- gradient of the predicted mean (seam S3g) ------------------------------------------------------
+// gs[q] = sum_i alpha_i amp grad_x k(x - X_i) at x = Xs_q: the sum above with the kernel's derivative in place of its value.
+// With d = Xs_q - X_i and M = invLam, grad k = -k M d (Gaussian) and -w(u) M d (von Karman, u^2 = d^T M d, w = -f'(u) / u from
+// bessel_k16.h; the isotropic kind has M = I / ell^2).  A pair at u == 0 contributes exactly 0: M d = 0 there for the Gaussian
+// kinds and the von Karman field has zero slope on a star (w is not evaluated).  Same decomposition as predict_partial_kernel;
+// two accumulators per thread (the components), their partial sums stored as two planes of ms queries per split.
+template <int KE>
+__global__ __launch_bounds__(256) void predict_grad_partial_kernel(KParams p, const double *__restrict__ X, int64_t n,
+                                                                   const double *__restrict__ alpha,
+                                                                   const double *__restrict__ Xs, int64_t m,
+                                                                   double *__restrict__ partial, int64_t chunk) {
+    __shared__ double sx[PT], sy[PT], sa[PT];
+    __shared__ double vk_tab[KE == KE_GAUSS ? 1 : 6 * K16_NDEG];       // von Karman: the K_{1/6} Chebyshev table, gathered per lane
+    if constexpr (KE != KE_GAUSS) vonkarman_slope_stage_table(vk_tab); // (the first barrier of the loop below publishes it)
+    const int tid = threadIdx.x;
+    const int64_t q = (int64_t)blockIdx.x * 256 + tid;
+    const int64_t i_begin = (int64_t)blockIdx.y * chunk;
+    const int64_t i_end = (i_begin + chunk < n) ? i_begin + chunk : n;
+    // M = [[a, b], [b, c]]; the isotropic von Karman kind keeps u = |d| / ell as the value does
+    const double ma = (KE == KE_VK) ? p.inv_ell * p.inv_ell : p.a, mb = (KE == KE_VK) ? 0.0 : 0.5 * p.b2, mc = (KE == KE_VK) ? ma : p.c;
+    double xq = 0.0, yq = 0.0;
+    if (q < m) { xq = Xs[2 * q]; yq = Xs[2 * q + 1]; }
+    constexpr int UNROLL = (KE == KE_GAUSS) ? 4 : 2;      // von Karman: 4 evaluations in flight take 143 VGPRs (3 waves per SIMD)
+    double accx = 0.0, accy = 0.0;
+    auto pair = [&](int t) {
+        const double dx = xq - sx[t], dy = yq - sy[t];
+        const double gx = ma * dx + mb * dy, gy = mb * dx + mc * dy;            // M d;  d^T M d = dx gx + dy gy
+        double s;
+        if constexpr (KE == KE_GAUSS) {
+            s = exp(-0.5 * (dx * gx + dy * gy)) * sa[t];
+        } else {
+            const double u = (KE == KE_VK) ? sqrt(dx * dx + dy * dy) * p.inv_ell : sqrt(dx * gx + dy * gy);
+            s = (u == 0.0) ? 0.0 : vonkarman_slope_tab(u, vk_tab) * sa[t];
+        }
+        accx = fma(s, gx, accx);
+        accy = fma(s, gy, accy);
+    };
+    for (int64_t i0 = i_begin; i0 < i_end; i0 += PT) {
+        const int64_t i = i0 + tid;
+        __syncthreads();
+        if (i < i_end) { sx[tid] = X[2 * i]; sy[tid] = X[2 * i + 1]; sa[tid] = alpha[i]; }
+        else { sx[tid] = 0.0; sy[tid] = 0.0; sa[tid] = 0.0; }
+        __syncthreads();
+        const int cnt = (int)((i_end - i0 < PT) ? (i_end - i0) : PT);
+        if (cnt == PT) {
+#pragma unroll UNROLL
+            for (int t = 0; t < PT; ++t) pair(t);
+        } else {
+            for (int t = 0; t < cnt; ++t) pair(t);
+        }
+    }
+    if (q < m) {
+        partial[((int64_t)blockIdx.y * 2) * m + q] = accx;
+        partial[((int64_t)blockIdx.y * 2 + 1) * m + q] = accy;
+    }
+}
+
+// Gaussian fast path: in the transformed coordinates of predict_gauss_tab_kernel k = 2^(-|dU|^2 / NT), so
+// grad_U k = -(2 ln 2 / NT) dU k: the kernel accumulates sum alpha k dU, two more FMAs per pair than the value (the product
+// k alpha, which the value folds into its one FMA, and the second component); the reduction applies T^T and the scale.
+// Identical transformed coordinates give dU = 0 exactly, so a query on a training point gets no slope from it.
+__global__ __launch_bounds__(256) void predict_grad_gauss_tab_kernel(const double *__restrict__ U, int64_t n,
+                                                                     const double *__restrict__ alpha,
+                                                                     const double *__restrict__ Us, int64_t m,
+                                                                     double *__restrict__ partial, int64_t chunk) {
+    constexpr int NT = 256;
+    __shared__ double sx[PT], sy[PT], sa[PT];
+    __shared__ double tab[NT];
+    const int tid = threadIdx.x;
+    tab[tid] = EXP2_J256[tid];
+    const int64_t q = (int64_t)blockIdx.x * 256 + tid;
+    const int64_t i_begin = (int64_t)blockIdx.y * chunk;
+    const int64_t i_end = (i_begin + chunk < n) ? i_begin + chunk : n;
+    double xq = 0.0, yq = 0.0;
+    if (q < m) { xq = Us[2 * q]; yq = Us[2 * q + 1]; }
+    double accx = 0.0, accy = 0.0;
+    for (int64_t i0 = i_begin; i0 < i_end; i0 += PT) {
+        const int64_t i = i0 + tid;
+        __syncthreads();
+        if (i < i_end) { sx[tid] = U[2 * i]; sy[tid] = U[2 * i + 1]; sa[tid] = alpha[i]; }
+        else { sx[tid] = 0.0; sy[tid] = 0.0; sa[tid] = 0.0; }          // alpha = 0: padded entries add nothing
+        __syncthreads();
+#pragma unroll 4
+        for (int t = 0; t < PT; ++t) {
+            const double dx = xq - sx[t], dy = yq - sy[t];
+            const double s = exp2_neg_tab<NT>(fma(dx, dx, dy * dy), tab) * sa[t];
+            accx = fma(s, dx, accx);
+            accy = fma(s, dy, accy);
+        }
+    }
+    if (q < m) {
+        partial[((int64_t)blockIdx.y * 2) * m + q] = accx;
+        partial[((int64_t)blockIdx.y * 2 + 1) * m + q] = accy;
+    }
+}
+
+// gs[q] = R (sum over the splits, in order), R = [[r00, 0], [r10, r11]]: -amp I, or -amp (2 ln 2 / NT) T^T for the fast path
+__global__ __launch_bounds__(256) void predict_grad_reduce_kernel(const double *__restrict__ partial, int64_t m, int nsplit,
+                                                                  double r00, double r10, double r11, double *__restrict__ gs) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= m) return;
+    double s0 = 0.0, s1 = 0.0;
+    for (int k = 0; k < nsplit; ++k) {
+        s0 += partial[((int64_t)k * 2) * m + q];
+        s1 += partial[((int64_t)k * 2 + 1) * m + q];
+    }
+    gs[2 * q] = r00 * s0;
+    gs[2 * q + 1] = (r10 == 0.0) ? r11 * s1 : r10 * s0 + r11 * s1;
+}
 }  // namespace
 
 int launch_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
@@ -305,6 +415,60 @@ int launch_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t
         default: predict_partial_kernel<KE_AVK><<<grid, block, 0, ctx->stream>>>(p, d_X, n, d_alpha, d_Xs, m, partial, chunk); break;
     }
     predict_reduce_kernel<<<(unsigned)qblocks, 256, 0, ctx->stream>>>(partial, m, (int)nsplit, 1.0, d_ys);
+    TGP_HIP(hipGetLastError());
+    return 0;
+}
+
+// The split of the training set depends on n alone and the queries go through in slabs of GRAD_SLAB, so that a query's bits
+// depend on nothing but the training set and its own coordinates (not on m, not on its position among the queries).  A slab is
+// 128 query blocks x up to 128 splits = 16 384 workgroups, the count launch_predict settled on; its partial sums take <= 64 MiB.
+int launch_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
+                        const double *d_Xs, int64_t m, double *d_gs) {
+    constexpr int64_t GRAD_SLAB = 32768, GRAD_MAXSPLIT = 128;
+    TGP_ARG(kind_to_ke(k->kind) >= 0);
+    TGP_ARG(n > 0 && m > 0);
+    const int ke = kind_to_ke(k->kind);
+    const KParams p = make_kparams(k);
+    int64_t nsplit = (n + PT - 1) / PT;
+    if (nsplit > GRAD_MAXSPLIT) nsplit = GRAD_MAXSPLIT;
+    int64_t chunk = (n + nsplit - 1) / nsplit;
+    chunk = (chunk + PT - 1) / PT * PT;
+    nsplit = (n + chunk - 1) / chunk;
+    const int64_t slab = (m < GRAD_SLAB) ? m : GRAD_SLAB;
+    auto rup = [](size_t b) { return (b + 255) / 256 * 256; };
+    int rc = tgp_ensure_scratch(ctx, rup((size_t)nsplit * 2 * slab * 8) + rup(2 * n * 8) + rup(2 * m * 8));
+    if (rc) return rc;
+    double *partial = (double *)ctx->scratch;
+    static const bool no_fast = getenv("TGP_PREDICT_GENERIC") != nullptr;
+    // invLam = L L^T (2x2 Cholesky); 1-D kernels have c = b = 0, i.e. l11 = 0
+    const double l00 = (k->a > 0.0) ? sqrt(k->a) : 0.0;
+    const double l10 = (l00 > 0.0) ? k->b / l00 : 0.0;
+    const double d11 = k->c - l10 * l10;
+    const bool fast = ke == KE_GAUSS && !no_fast && l00 > 0.0 && d11 >= 0.0;
+    double r00 = -k->amp, r10 = 0.0, r11 = -k->amp;
+    const double *U = nullptr, *Us = nullptr;
+    if (fast) {
+        const double sc = 0.84932180028801904272 * 16.0;                 // sqrt(0.5 log2 e NT), NT = 256
+        const double t00 = sc * l00, t10 = sc * l10, t11 = sc * sqrt(d11);
+        double *Ub = (double *)((char *)ctx->scratch + rup((size_t)nsplit * 2 * slab * 8));
+        double *Usb = (double *)((char *)Ub + rup(2 * n * 8));
+        predict_transform_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(d_X, n, d_X, t00, t10, t11, Ub);
+        predict_transform_kernel<<<(unsigned)((m + 255) / 256), 256, 0, ctx->stream>>>(d_Xs, m, d_X, t00, t10, t11, Usb);
+        const double g = -k->amp * (2.0 * 0.69314718055994530942 / 256.0);
+        r00 = g * t00; r10 = g * t10; r11 = g * t11;
+        U = Ub; Us = Usb;
+    }
+    for (int64_t q0 = 0; q0 < m; q0 += GRAD_SLAB) {
+        const int64_t ms = (m - q0 < GRAD_SLAB) ? m - q0 : GRAD_SLAB;
+        const unsigned qblocks = (unsigned)((ms + 255) / 256);
+        dim3 grid(qblocks, (unsigned)nsplit), block(256);
+        const double *xs = d_Xs + 2 * q0;
+        if (fast) predict_grad_gauss_tab_kernel<<<grid, block, 0, ctx->stream>>>(U, n, d_alpha, Us + 2 * q0, ms, partial, chunk);
+        else if (ke == KE_GAUSS) predict_grad_partial_kernel<KE_GAUSS><<<grid, block, 0, ctx->stream>>>(p, d_X, n, d_alpha, xs, ms, partial, chunk);
+        else if (ke == KE_VK) predict_grad_partial_kernel<KE_VK><<<grid, block, 0, ctx->stream>>>(p, d_X, n, d_alpha, xs, ms, partial, chunk);
+        else predict_grad_partial_kernel<KE_AVK><<<grid, block, 0, ctx->stream>>>(p, d_X, n, d_alpha, xs, ms, partial, chunk);
+        predict_grad_reduce_kernel<<<qblocks, 256, 0, ctx->stream>>>(partial, ms, (int)nsplit, r00, r10, r11, d_gs + 2 * q0);
+    }
     TGP_HIP(hipGetLastError());
     return 0;
 }

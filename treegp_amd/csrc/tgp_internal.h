@@ -269,6 +269,9 @@ int launch_extract_row(tgp_ctx *ctx, const double *d_A, int64_t Np, int64_t n, d
 int launch_logdet_rowsq(tgp_ctx *ctx, const double *d_A, int64_t Np, int64_t n, double *d_out);
 int launch_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
                    const double *d_Xs, int64_t m, double *d_ys);
+// gradient of the predicted mean with respect to the query point: d_gs (m, 2)
+int launch_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
+                        const double *d_Xs, int64_t m, double *d_gs);
 int launch_unpack_lower(tgp_ctx *ctx, const double *d_A, int64_t Np, int64_t n, double *d_out);
 int launch_pack_lower(tgp_ctx *ctx, const double *d_K, int64_t n, int64_t Np, const double *d_yerr, double *d_A);
 // d_B: (nrhs, Np) right-hand sides, solved in place, the factor read once per sweep for groups of up to 8 of them

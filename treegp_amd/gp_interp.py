@@ -203,6 +203,25 @@ class GPInterpolation(object):
             return y_predict, ops.gp_predict_var_dense(self._factor, HT, kernel.diag(X2))
         return y_predict, None
 
+    def predict_gradient(self, X):
+        """Spatial derivative of the interpolated field at X (n_samples, 1 or 2): (n_samples, ndim), column c the derivative
+        along coordinate c of the GP part of what ``predict(X)`` returns, from the kernel's analytic derivative
+        (ops.gp_predict_grad) instead of differences of ``predict`` at shifted points.  Not in the reference.  The constant
+        ``_mean`` of ``normalize`` drops out; a KNN mean function is piecewise constant and contributes nothing (its jumps
+        between neighbourhoods are not a slope).  A von Karman field has a cusp on every star: the slope reported there is
+        zero.  Uses the cached ``_alpha`` under the rules of ``predict`` (solved for on first use, no factor is kept).
+        Kernels of the dense route (anything ``kernel_to_spec`` does not describe) have no device form of their derivative:
+        NotImplementedError.  Runs on one GPU whichever backend solved."""
+        try:
+            spec = kernel_to_spec(self.kernel)
+        except NotImplementedError:
+            raise NotImplementedError("predict_gradient needs a kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
+                                      "AnisotropicVonKarman, optionally times a constant); got %r" % (self.kernel,))
+        with self._scope():
+            self._ensure_solution(self._residual(), self._X, self.kernel, spec, self._y_err, want_factor=False)
+        ndim = 1 if np.ndim(X) < 2 else np.shape(X)[1]
+        return ops.gp_predict_grad(spec, self._X, self._alpha, X)[:, :ndim]
+
     def sample_y(self, X, n_samples=1, random_state=0, nugget=1e-10):
         """Realisations of the posterior at X (n_points, 1 or 2): (n_points, n_samples), scikit-learn's ``sample_y``
         layout (not in the reference).  y_star + L* z with y_star, cov = ``predict(X, return_cov=True)`` (mean, meanify and

@@ -456,6 +456,21 @@ def gp_predict(spec, X, alpha, Xs, ctx=None):
     return ys
 
 
+def gp_predict_grad(spec, X, alpha, Xs, ctx=None):
+    """(m, 2): the derivative with respect to the query point of what ``gp_predict`` returns, d/dXs [k(Xs, X) @ alpha], from the
+    kernel's analytic derivative (tgp_gp_predict_grad, seam S3g of include/tgp.h).  A training point at zero distance from a
+    query contributes no slope; 1-D coordinates give a zero second column.  Runs on this process's GPU whatever the multi-GPU
+    settings: the sum is one pass over the pairs, as ``gp_predict``'s."""
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    X2, Xs2 = as_xy(X), as_xy(Xs)
+    alpha = f64(alpha)
+    gs = np.empty((Xs2.shape[0], 2))
+    rc = lib.tgp_gp_predict_grad(ctx, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(Xs2), Xs2.shape[0], ptr(gs))
+    check(ctx, rc, "tgp_gp_predict_grad")
+    return gs
+
+
 def gp_predict_cov(spec, factor, X, Xs, ctx=None):
     """Posterior covariance k(Xs,Xs) - HT K^-1 HT^T (gp_interp.py:184-192) from a kept factor."""
     ctx = ctx or factor._ctx
