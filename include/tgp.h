@@ -257,6 +257,22 @@ int tgp_factor_lmul(tgp_ctx *ctx, tgp_factor *f, const double *Z, int nrhs, doub
  * Timings: [3] device compute, [9] transfer, each summed over the chunks.                                              */
 int tgp_factor_inv_diag(tgp_ctx *ctx, tgp_factor *f, double *d);
 
+/* ---- S3h: diagonal blocks of K^-1 -- what leaving a GROUP of points out of a GP needs (R&W 5.4.2 with blocks for points:
+ * with P = (K + diag(yerr^2))^-1 and alpha = P r, the points G predicted from all the others have mean r_G - P_GG^-1 alpha_G,
+ * covariance P_GG^-1 and log p(y_G | y_-G) = -g/2 log 2 pi + 1/2 log det P_GG - 1/2 alpha_G^T P_GG^-1 alpha_G).
+ * Group g is rows [starts[g], starts[g+1]) of the problem of a factor kept by tgp_gp_solve / tgp_gp_solve_dense /
+ * tgp_factor_borrow: starts holds ngroups + 1 strictly increasing values, starts[0] == 0, starts[ngroups] == n, every group at
+ * most TGP_INVBLOCK_GMAX rows.  blocks receives the groups' blocks one after the other, block g a row-major g x g array at
+ * offset sum_{h<g} g_h^2; both triangles are written and are equal bit for bit.  [P]_ij = Bt_i . Bt_j over the rows of
+ * Bt = L^-T that S3e makes (same chunks of identity rows, TGP_INVDIAG_CHUNK raised to the largest group plus one step; a group
+ * never straddles two chunks), summed on the fp64 matrix cores from the panel that holds the group's first row: ~n^3 / 3
+ * flops of substitution plus sum g^2 (n - starts[g]), no n x n buffer, no atomics.  A block's bits depend neither on the
+ * chunk nor on the other groups.  Returns -1 with a message naming the entry for a NULL pointer, ngroups < 1, starts that do
+ * not increase or do not span [0, n], or a group above the limit (nothing has run on the device then); -2 for HIP errors.
+ * Timings: [3] device compute, [9] transfer, each summed over the chunks.                                              */
+#define TGP_INVBLOCK_GMAX 4096
+int tgp_factor_inv_blocks(tgp_ctx *ctx, tgp_factor *f, const int64_t *starts, int64_t ngroups, double *blocks);
+
 /* ---- S2d: gradient of the log marginal likelihood from a kept factor and its alpha ---------
  * (the reference's optimiser passes no jac, treegp/log_likelihood.py:57 -- this is what a caller who wants one
  * gets, in the kernel-derivative convention of treegp/kernels.py:128-150.)

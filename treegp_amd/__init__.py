@@ -16,7 +16,9 @@ from .meanify import meanify  # noqa: F401
 from .utils import comp_eb, comp_eb_treecorr
 from .sampling import gaussian_random_field
 from .fit_many import solve_many
+from .loo import kfold_labels, spatial_block_labels
 
 __all__ = ["__version__", "__version_info__", "GPInterpolation", "two_pcf", "log_likelihood", "AnisotropicRBF",
            "VonKarman", "AnisotropicVonKarman", "eval_kernel", "kernel_to_spec", "meanify", "comp_eb", "comp_eb_treecorr",
-           "gaussian_random_field", "predict_many", "solve_many", "predict_loo_many", "loo_log_predictive_many"]
+           "gaussian_random_field", "predict_many", "solve_many", "predict_loo_many", "loo_log_predictive_many",
+           "kfold_labels", "spatial_block_labels"]

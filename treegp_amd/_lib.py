@@ -73,6 +73,7 @@ SIGNATURES = {
     "tgp_factor_solve": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "tgp_factor_lmul": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp]),
     "tgp_factor_inv_diag": (C.c_int, [_vp, _vp, _vp]),
+    "tgp_factor_inv_blocks": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "tgp_gp_solve_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_solve_grad_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_loo_batch": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

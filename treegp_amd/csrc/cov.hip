@@ -447,6 +447,171 @@ extern "C" int tgp_factor_inv_diag(tgp_ctx *ctx, tgp_factor *f, double *d) {
     return 0;
 }
 
+// ---- diagonal blocks of K^-1 from a kept factor (seam S3h): P_GG = Bt_G Bt_G^T for groups G of contiguous rows ------------------
+// What leaving a GROUP of points out of a GP needs (Rasmussen & Williams 5.4.2 with blocks for points).  The rows of Bt = E L^-T
+// are made exactly as for tgp_factor_inv_diag (ident_chunk_kernel, cov_substitute with `tri`, both substitutions); where that
+// keeps the squared norm of every row, this keeps the Gram matrix of every group's rows.  A chunk starts at the largest multiple
+// of the substitution's step at or below the first row of the first group that is not done and finishes every group that lies
+// wholly inside it, so a group never straddles two chunks (at most step - 1 rows and one partial group are substituted twice per
+// chunk); the chunk is TGP_INVDIAG_CHUNK rows or its default, raised to the largest group plus one step where that is more.
+// Per chunk: one launch of the fp64 MFMA tile product over the lower tile pairs of every finished group's 128-row tiles
+// (global tiles: a group that starts or ends inside one uses the tiles that cover it), every sum from the panel that holds the
+// group's first row -- left of it those rows are zero, and a chunk that begins there does not even store them -- then one
+// launch that drops the rows outside the groups, negates and mirrors the lower triangles into the row-major blocks.  No
+// atomics; an entry's terms and their order depend on its group alone: neither on the chunk size nor on the other groups.
+// Memory beside the chunk's Bt: 128 KiB per tile pair and the chunk's blocks (sum of g^2 doubles), in the context's io buffer.
+namespace {
+__global__ __launch_bounds__(256, 2) void inv_blocks_syrk_kernel(double *C, const double *Bt, int64_t Mp, const InvBlockItem *items) {
+    inv_block_syrk_tile(C, Bt, Mp, items, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void inv_blocks_write_kernel(const double *C, const InvBlockItem *items, double *out) {
+    inv_block_write_tile(C, items, blockIdx.x, out);
+}
+
+struct InvBlockChunk {
+    int64_t c0, rows;            // first row (a multiple of the step) and rows substituted
+    int64_t item0, nitems;       // its tile pairs in the item table
+    int64_t out0, outlen;        // its groups' blocks in the caller's array (doubles)
+};
+
+int inv_blocks_check(tgp_ctx *ctx, const tgp_factor *f, const int64_t *starts, int64_t ngroups, const double *blocks) {
+    static const std::string fn = "tgp_factor_inv_blocks: ";
+    auto s = [](int64_t v) { return std::to_string((long long)v); };
+    if (!(f && starts && blocks)) { ctx->err = fn + "f, starts and blocks must not be NULL"; return -1; }
+    if (ngroups < 1) { ctx->err = fn + "ngroups = " + s(ngroups) + " must be >= 1"; return -1; }
+    if (starts[0] != 0) { ctx->err = fn + "starts[0] = " + s(starts[0]) + " must be 0"; return -1; }
+    for (int64_t g = 0; g < ngroups; ++g) {
+        if (starts[g + 1] <= starts[g]) {
+            ctx->err = fn + "starts[" + s(g + 1) + "] = " + s(starts[g + 1]) + " is not above starts[" + s(g) + "] = " + s(starts[g]);
+            return -1;
+        }
+        if (starts[g + 1] - starts[g] > TGP_INVBLOCK_GMAX) {
+            ctx->err = fn + "group " + s(g) + " (starts[" + s(g) + "] = " + s(starts[g]) + " to starts[" + s(g + 1) + "] = " +
+                       s(starts[g + 1]) + ") has more than TGP_INVBLOCK_GMAX = " + s(TGP_INVBLOCK_GMAX) + " rows";
+            return -1;
+        }
+    }
+    if (starts[ngroups] != f->n) {
+        ctx->err = fn + "starts[" + s(ngroups) + "] = " + s(starts[ngroups]) + " must be the factor's n = " + s(f->n);
+        return -1;
+    }
+    return 0;
+}
+
+// the chunks and the tile pairs of every group (host only).  R: rows per chunk, a multiple of `step`, at least the largest group
+// plus step - 1 unless it covers all n rows
+void inv_blocks_layout(const int64_t *starts, int64_t ngroups, int64_t n, int64_t Np, int64_t step, int64_t R,
+                       std::vector<InvBlockChunk> *chunks, std::vector<InvBlockItem> *items) {
+    const int nP = (int)(Np / TGP_PW);
+    int64_t g = 0, out = 0;
+    while (g < ngroups) {
+        InvBlockChunk ch;
+        ch.c0 = starts[g] / step * step;
+        ch.rows = (n - ch.c0) < R ? (n - ch.c0) : R;
+        ch.item0 = (int64_t)items->size();
+        ch.out0 = out;
+        const int64_t pb = ch.c0 >> 8;
+        int64_t local = 0;
+        for (; g < ngroups && starts[g + 1] <= ch.c0 + ch.rows; ++g) {
+            const int64_t ls = starts[g] - ch.c0, le = starts[g + 1] - ch.c0, gs = le - ls;
+            const int64_t t0 = ls / TGP_TB, t1 = (le - 1) / TGP_TB;
+            for (int64_t ti = t0; ti <= t1; ++ti)
+                for (int64_t tj = t0; tj <= ti; ++tj) {
+                    InvBlockItem it;
+                    it.ta = (int)ti; it.tb = (int)tj;
+                    it.p0 = (int)((starts[g] >> 8) - pb);
+                    it.nseg = nP - (int)(starts[g] >> 8);
+                    it.ra = (int)(ti * TGP_TB - ls); it.rb = (int)(tj * TGP_TB - ls);
+                    it.g = (int)gs; it.pad = 0;
+                    it.out = local;
+                    items->push_back(it);
+                }
+            local += gs * gs;
+        }
+        ch.nitems = (int64_t)items->size() - ch.item0;
+        ch.outlen = local;
+        out += local;
+        chunks->push_back(ch);
+    }
+}
+}  // namespace
+
+extern "C" int tgp_factor_inv_blocks(tgp_ctx *ctx, tgp_factor *f, const int64_t *starts, int64_t ngroups, double *blocks) {
+    if (!ctx) return -1;
+    int rc = inv_blocks_check(ctx, f, starts, ngroups, blocks);
+    if (rc) return rc;
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t n = f->n;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));                   // (the first chunk's interval includes building the slabs)
+    int S = 0;
+    const double *slabs = nullptr;
+    rc = cov_step(ctx, f, &S, &slabs);
+    if (rc) return rc;
+    const int64_t step = S ? S : TGP_PW;
+    int64_t R = 0, gmax = 0;
+    rc = inv_diag_chunk_rows(ctx, f, step, &R);
+    if (rc) return rc;
+    for (int64_t g = 0; g < ngroups; ++g) gmax = starts[g + 1] - starts[g] > gmax ? starts[g + 1] - starts[g] : gmax;
+    const int64_t fits = (gmax + 2 * step - 1) / step * step;  // a group that starts step - 1 rows into its chunk still ends inside
+    if (R < fits) R = fits;
+    std::vector<InvBlockChunk> chunks;
+    std::vector<InvBlockItem> items;
+    inv_blocks_layout(starts, ngroups, n, f->Np, step, R, &chunks, &items);
+    int64_t most_items = 0, most_out = 0;
+    for (const InvBlockChunk &ch : chunks) {
+        most_items = ch.nitems > most_items ? ch.nitems : most_items;
+        most_out = ch.outlen > most_out ? ch.outlen : most_out;
+    }
+    CovPlan pl;
+    rc = cov_plan(ctx, f, n, false, &pl, R < f->Np ? R : f->Np);   // d_Bt: the largest chunk, at most Np x Np
+    if (rc) return rc;
+    // io buffer: the item table | the tile slots of one chunk (an even number: two per strip) | one chunk's blocks
+    const size_t tab_bytes = rup(items.size() * sizeof(InvBlockItem));
+    const size_t slot_bytes = rup((size_t)((most_items + 1) / 2) * TGP_TB * TGP_PW * sizeof(double));
+    rc = tgp_ensure_io(ctx, tab_bytes + slot_bytes + rup((size_t)most_out * sizeof(double)));
+    if (rc) return rc;
+    InvBlockItem *d_items = (InvBlockItem *)tgp_io_buffer(ctx);
+    double *d_C = (double *)((char *)tgp_io_buffer(ctx) + tab_bytes);
+    double *d_out = (double *)((char *)d_C + slot_bytes);
+    void *pin = nullptr;
+    rc = tgp_ensure_pinned(ctx, items.size() * sizeof(InvBlockItem), &pin);
+    if (rc) return rc;
+    memcpy(pin, items.data(), items.size() * sizeof(InvBlockItem));
+    TGP_HIP(hipMemcpyAsync(d_items, pin, items.size() * sizeof(InvBlockItem), hipMemcpyHostToDevice, st));
+    double t_dev = 0.0, t_d2h = 0.0;
+    bool first = true;
+    for (const InvBlockChunk &ch : chunks) {
+        CovPlan cp = pl;
+        cp.Mp = (ch.rows + TGP_PW - 1) / TGP_PW * TGP_PW;
+        cp.nPm = (int)(cp.Mp / TGP_PW);
+        cp.c0 = ch.c0;
+        const int np = cp.nP - (int)(cp.c0 >> 8);               // panels the chunk stores
+        if (!first) TGP_HIP(hipEventRecord(ctx->ev[0], st));
+        first = false;
+        TGP_HIP(hipMemsetAsync(cp.d_Bt, 0, (size_t)cp.Mp * np * TGP_PW * 8, st));
+        ident_chunk_kernel<<<(unsigned)(cp.Mp / 256), 256, 0, st>>>(cp.d_Bt, cp.Mp, cp.c0);
+        rc = cov_substitute(ctx, f, cp, true);
+        if (rc) return rc;
+        TGP_HIP(hipMemsetAsync(d_C, 0, (size_t)((ch.nitems + 1) / 2) * TGP_TB * TGP_PW * sizeof(double), st));
+        inv_blocks_syrk_kernel<<<(unsigned)ch.nitems, 256, 0, st>>>(d_C, cp.d_Bt, cp.Mp, d_items + ch.item0);
+        inv_blocks_write_kernel<<<(unsigned)ch.nitems, 256, 0, st>>>(d_C, d_items + ch.item0, d_out);
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipEventRecord(ctx->ev[1], st));
+        TGP_HIP(hipMemcpyAsync(blocks + ch.out0, d_out, (size_t)ch.outlen * 8, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipEventRecord(ctx->ev[2], st));
+        TGP_HIP(hipStreamSynchronize(st));
+        float ms = 0.f;
+        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        t_dev += ms;
+        TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+        t_d2h += ms;
+    }
+    ctx->timings[3] = t_dev;                    // device compute
+    ctx->timings[9] = t_d2h;                    // the blocks to the caller's buffer
+    return 0;
+}
+
 // ---- gradient of the log marginal likelihood (kernel derivative convention of treegp/kernels.py:128-150) ------------
 //   dlogL/dp = 1/2 sum_ij (alpha_i alpha_j - [K^-1]_ij) dK_ij/dp
 // for the four numbers a Gaussian kernel is made of on the device: p = log amp, a, b, c (invLam 00, 01 = 10, 11); the chain rule

@@ -46,6 +46,46 @@ __device__ __forceinline__ void post_syrk_tile(double *C, const double *Bt, int6
     gemm_tile_dtv<4, TGP_PW, 0>(a, b, c, nullptr, nullptr, nP - (int)p0, Mp * TGP_PW, Mp * TGP_PW);
 }
 
+// ---- diagonal blocks of (K + D)^-1 (seam S3h): [P]_ij = Bt_i . Bt_j over the rows of one group -----------------------------------
+// One 128 x 128 tile pair of one group's block.  The items are laid out by the host (cov.hip: tgp_factor_inv_blocks); item q
+// owns tile slot q of the staging buffer C: two slots side by side per 128 x 256 strip (ld 256), as the tiles of a panel.
+struct InvBlockItem {
+    int ta, tb;      // 128-row tiles of the chunk's Bt, ta >= tb
+    int p0, nseg;    // first stored panel the sum covers (the one that holds the group's first row) and how many follow
+    int ra, rb;      // row of the group's block that row 0 of tile ta / tb is (negative: the tile starts above the group)
+    int g, pad;      // rows of the group
+    int64_t out;     // where the group's g x g block starts in the chunk's output
+};
+__device__ __forceinline__ double *inv_block_slot(double *C, int64_t q) {
+    return C + (q >> 1) * TGP_TB * TGP_PW + (q & 1) * TGP_TB;
+}
+// slot q of C (zero before) <- -sum over the panels p0 .. p0 + nseg - 1 of Bt[ta] Bt[tb]^T: post_syrk_tile's product, with ONE
+// first panel for every pair of a group, so that an entry's sum has the same terms in the same order wherever the group lies
+// in its chunk
+__device__ __forceinline__ void inv_block_syrk_tile(double *C, const double *Bt, int64_t Mp, const InvBlockItem *items, int64_t q) {
+    const int ta = __builtin_amdgcn_readfirstlane(items[q].ta), tb = __builtin_amdgcn_readfirstlane(items[q].tb);
+    const int p0 = __builtin_amdgcn_readfirstlane(items[q].p0), nseg = __builtin_amdgcn_readfirstlane(items[q].nseg);
+    const double *a = Bt + (int64_t)p0 * Mp * TGP_PW + (int64_t)ta * TGP_TB * TGP_PW;
+    const double *b = Bt + (int64_t)p0 * Mp * TGP_PW + (int64_t)tb * TGP_TB * TGP_PW;
+    gemm_tile_dtv<4, TGP_PW, 0>(a, b, inv_block_slot(C, q), nullptr, nullptr, nseg, Mp * TGP_PW, Mp * TGP_PW);
+}
+// the entries of slot q that belong to the group, negated (exact), into its row-major block: the lower triangle as computed
+// and its mirror image, so both halves carry the same bits.  Rows and columns of the tiles outside the group are dropped.
+// Every entry of the block is written by exactly one thread of one item: no atomics.
+__device__ __forceinline__ void inv_block_write_tile(const double *C, const InvBlockItem *items, int64_t q, double *out) {
+    const InvBlockItem it = items[q];
+    const double *c = inv_block_slot(const_cast<double *>(C), q);
+    double *blk = out + it.out;
+    for (int idx = threadIdx.x; idx < TGP_TB * TGP_TB; idx += 256) {
+        const int r = idx >> 7, col = idx & 127;
+        const int i = it.ra + r, j = it.rb + col;
+        if (i < 0 || i >= it.g || j < 0 || j > i) continue;
+        const double v = -c[r * TGP_PW + col];
+        blk[(int64_t)i * it.g + j] = v;
+        if (i != j) blk[(int64_t)j * it.g + i] = v;
+    }
+}
+
 // |Bt[i, :]|^2 over nP panels by one wave: each lane squares 2 + 2 doubles of every 256-wide panel row (two 16-byte loads,
 // 1 KiB contiguous per wave and load), lane partials run over the panels in order, then a fixed xor tree across the wave.
 // No atomics.  Every lane returns the sum.

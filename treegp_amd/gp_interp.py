@@ -15,7 +15,7 @@ from sklearn.neighbors import KNeighborsRegressor
 from . import ops
 from .fits_io import read_bintable_row
 from .kernels import eval_kernel, kernel_to_spec
-from .loo import loo_quantities
+from .loo import group_runs, lgo_quantities, loo_quantities
 
 
 class GPInterpolation(object):
@@ -320,6 +320,96 @@ class GPInterpolation(object):
                 total = float(np.sum(loo_quantities(r, alpha, d, self._y_err)[3]))
         except (np.linalg.LinAlgError, FloatingPointError, ValueError):
             total = -np.inf                    # as log_likelihood (log_likelihood.py:38-39 of the reference)
+        except TgpError as ex:
+            if not _rejects_theta(ex):
+                raise
+            total = -np.inf
+        return total if np.isfinite(total) else -np.inf
+
+    # -- leave-group-out (not in the reference) --------------------------------------------------
+    def _lgo_solve(self, kernel, perm, starts, want_cov):
+        """lgo_quantities of the problem permuted by ``perm`` (the groups contiguous) from a temporary factor of its own:
+        (mu, v, logp, covs) in the permuted order"""
+        X, r, sigma = self._X, self._residual(), self._y_err
+        if perm is not None:
+            X, r, sigma = X[perm], r[perm], np.asarray(sigma)[perm]
+        try:
+            spec = kernel_to_spec(kernel)
+        except NotImplementedError:
+            spec = None
+        with self._scope():
+            if spec is not None:
+                alpha, _, _, factor = ops.gp_solve(spec, X, r, sigma, keep=True)
+            else:
+                alpha, _, _, factor = ops.gp_solve_dense(kernel(X), r, sigma, keep=True)
+            try:
+                blocks = ops.factor_inv_blocks(factor, starts)
+            finally:
+                factor.free(keep_memory=True)
+            return lgo_quantities(r, alpha, blocks, sigma, starts, want_cov=want_cov)
+
+    def predict_lgo(self, groups, return_var=False, return_cov=False):
+        """Leave-group-out predictions at the positions given to ``initialize``.  ``groups``: one integer label per training
+        point, any labels (``kfold_labels``, ``spatial_block_labels``, a chip number, ...).  Entry i of y_lgo (n,) is what
+        ``predict(X[i:i+1])`` returns for a GP with the same kernel given every point OUTSIDE i's group: for a spatially
+        correlated field the held-out score that ``predict_loo`` flatters, since a deleted star's neighbours still carry
+        almost all of its information.  Closed form from alpha and the diagonal blocks of K^-1 (Rasmussen & Williams 5.4.2
+        with blocks for points; ops.factor_inv_blocks, one substitution on the device) instead of one refit per group.
+        ``return_var``: also the latent variances (n,), what ``predict(X[i:i+1], return_var=True)`` gives there;
+        ``return_cov``: also a dict label -> (indices, C_G) with the group's points and their latent covariance, what
+        ``predict(X[indices], return_cov=True)`` gives.  At most one of the two; nothing is clamped.  ``_mean`` and the mean
+        function are held at their full-data values, as in ``predict_loo``.
+        When every label occupies one contiguous run of rows (catalogues concatenated chip by chip) the cached ``_alpha`` and
+        the kept factor serve under ``predict_loo``'s rules.  Otherwise the problem permuted by the stable sort by label is
+        solved on a temporary factor, and ``_alpha`` and the kept factor stay untouched.  Any kernel tree works.
+        ValueError for labels of the wrong length or a group above 4096 points (naming the label)."""
+        if return_cov and return_var:
+            raise ValueError("at most one of return_cov and return_var may be True")
+        n = len(self._X)
+        labels = np.asarray(groups)
+        if labels.shape != (n,):
+            raise ValueError("groups must hold one label per training point, shape (%d,); got %r" % (n, labels.shape))
+        perm, starts, names = group_runs(labels, gmax=ops.INVBLOCK_GMAX)
+        if perm is None:
+            r = self._residual()
+            try:
+                spec = kernel_to_spec(self.kernel)
+            except NotImplementedError:
+                spec = None
+            with self._scope():
+                self._ensure_solution(r, self._X, self.kernel, spec, self._y_err, want_factor=True)
+                blocks = ops.factor_inv_blocks(self._factor, starts)
+                mu, v, _, covs = lgo_quantities(r, self._alpha, blocks, self._y_err, starts, want_cov=return_cov)
+            index = np.arange(n)
+        else:
+            mu_p, v_p, _, covs = self._lgo_solve(self.kernel, perm, starts, return_cov)
+            mu, v = np.empty(n), np.empty(n)
+            mu[perm], v[perm] = mu_p, v_p
+            index = perm
+        y_lgo = mu + self._mean + self._spatial_average
+        if return_cov:
+            return y_lgo, {names[g].item(): (index[starts[g]:starts[g + 1]].copy(), covs[g]) for g in range(len(names))}
+        return (y_lgo, v) if return_var else y_lgo
+
+    def return_lgo_log_predictive(self, groups, theta=None):
+        """sum over the groups of log p(y_G | y_-G) for the current (or the given) hyper-parameters: the held-out score of
+        ``predict_lgo``'s folds, comparable between optimisers and kernels.  Mirrors ``return_loo_log_predictive``: a
+        temporary factor of its own, ``_alpha`` and the kept factor are left untouched; -inf when the factorisation fails."""
+        from ._lib import TgpError
+        from .log_likelihood import _rejects_theta
+        n = len(self._X)
+        labels = np.asarray(groups)
+        if labels.shape != (n,):
+            raise ValueError("groups must hold one label per training point, shape (%d,); got %r" % (n, labels.shape))
+        perm, starts, _ = group_runs(labels, gmax=ops.INVBLOCK_GMAX)
+        kernel = copy.deepcopy(self.kernel)
+        if theta is not None:
+            kernel = kernel.clone_with_theta(theta)
+        try:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                total = float(np.sum(self._lgo_solve(kernel, perm, starts, False)[2]))
+        except (np.linalg.LinAlgError, FloatingPointError, ValueError):
+            total = -np.inf                    # as return_loo_log_predictive
         except TgpError as ex:
             if not _rejects_theta(ex):
                 raise

@@ -350,6 +350,35 @@ def factor_inv_diag(factor, ctx=None):
     return d
 
 
+INVBLOCK_GMAX = 4096   # tgp_factor_inv_blocks: most rows of one group (TGP_INVBLOCK_GMAX)
+
+
+def factor_inv_blocks(factor, starts, ctx=None):
+    """The diagonal blocks of (K + D)^-1 from a kept factor (tgp_factor_inv_blocks): group g is rows starts[g] .. starts[g+1] - 1,
+    starts (ngroups + 1,) integers.  Returns a list of (g, g) arrays, each symmetric bit for bit.  With alpha = (K + D)^-1 r they
+    give every group's prediction from the points outside it (treegp_amd.loo.lgo_quantities).  The factor and the shape of
+    ``starts`` are checked here (ValueError); its values -- increasing from 0 to n, no group above 4096 rows -- by the library
+    before anything runs on the device (TgpError naming the entry)."""
+    if factor is None or not factor._h:
+        raise ValueError("factor_inv_blocks needs a kept factor (gp_solve(..., keep=True)) that has not been freed")
+    s = np.asarray(starts)
+    if s.ndim != 1 or s.shape[0] < 2 or s.dtype.kind not in "iu":
+        raise ValueError("factor_inv_blocks: starts must be a 1-D integer array of ngroups + 1 >= 2 entries, got %s %r"
+                         % (s.dtype, s.shape))
+    s = np.ascontiguousarray(s, dtype=np.int64)
+    sizes = np.diff(s)
+    # values the library will refuse get no buffer sized by them
+    valid = s[0] == 0 and s[-1] == factor.n and np.all(sizes > 0) and np.all(sizes <= INVBLOCK_GMAX)
+    flat = np.empty(int(np.sum(sizes * sizes)) if valid else 1)
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    check(ctx, lib.tgp_factor_inv_blocks(ctx, factor._h, ptr(s), len(s) - 1, ptr(flat)), "tgp_factor_inv_blocks")
+    if not valid:
+        raise ValueError("factor_inv_blocks: the library accepted starts that this wrapper holds invalid")
+    offs = np.concatenate([[0], np.cumsum(sizes * sizes)])
+    return [flat[offs[g]:offs[g + 1]].reshape(int(sizes[g]), int(sizes[g])) for g in range(len(sizes))]
+
+
 def gp_predict_cov_dense(factor, HT, Kss, ctx=None):
     """Kss - HT (K + D)^-1 HT^T for caller-evaluated HT = kernel(X2, Y=X1) (m, n) and Kss = kernel(X2) (m, m)."""
     ctx = ctx or factor._ctx
