@@ -286,6 +286,35 @@ int tgp_gp_loglik_grad(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const d
 int tgp_d_gp_solve_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_y,
                         const double *d_yerr, double *logdet, double *ydota, double *grad);
 
+/* ---- S2h: S2d and S2f for all four kernel kinds: the exact likelihood gradient of the von Karman kernels ------------------
+ * Not in the reference: kernels.py:278-288 (VonKarman returns K times the distances, the derivative of nothing), 383-384
+ * (AnisotropicVonKarman raises "Gradient can not be evaluated"), so its fits of the atmospheric kernels difference the
+ * likelihood, ntheta + 1 factorisations per iteration.  With (dx, dy) = X_i - X_j, q = a dx^2 + 2 b dx dy + c dy^2, u = sqrt(q)
+ * (TGP_VK: a = c = 1 / ell^2, b = 0, u = |d| / ell as the value evaluates it), K_ij = amp f(u), f the profile of
+ * bessel_k56.h, w(u) = -f'(u) / u = 2 pi u^(-1/6) K_{1/6}(2 pi u) / lim0 (bessel_k16.h, as S3g) and
+ * m_ij = alpha_i alpha_j - [K^-1]_ij:
+ *   grad[0] =  1/2 sum_ij m_ij amp f(u_ij)            (diagonal: amp)
+ *   grad[1] = -1/4 sum_ij m_ij amp w(u_ij) dx^2
+ *   grad[2] = -1/2 sum_ij m_ij amp w(u_ij) dx dy
+ *   grad[3] = -1/4 sum_ij m_ij amp w(u_ij) dy^2
+ * for p = log amp, a, b, c in the convention and element order of S2d: its sums with exp(-q / 2) replaced by f in slot 0 and by
+ * w in slots 1 .. 3.  A pair of distinct points at u == 0 adds f = 1 to slot 0 and exactly 0 to the others (w(0) is infinite
+ * and never evaluated); beyond the value's cutoff (2 pi u > 697.87) f and w are exactly 0.  For TGP_VK the caller maps the
+ * four numbers to theta = log ell with the row [0, -2 / ell^2, 0, -2 / ell^2] (kernels.spec_jacobian).
+ * Arguments, limits, return codes, timings and chunking are those of the namesakes (S2d, S2f); an unknown kind returns -1 with
+ * a message naming the entry.  For TGP_RBF / TGP_ARBF the results are bit for bit the namesakes': the same kernels, the same
+ * launches.  In the batch the kinds may be mixed; a problem's bits depend neither on its companions (of whatever kind), nor on
+ * its place, nor on the chunking; logdet / ydota are tgp_gp_solve_batch's; a problem with info[b] > 0 leaves the others
+ * untouched.  The pair sum is O(n^2) beside the O(n^3) inverse: one exact evaluation costs the same ~3 factorisations'
+ * worth of flops for every kind.                                                                                            */
+int tgp_gp_loglik_grad_any(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n,
+                           const double *alpha, double *grad);
+int tgp_d_gp_solve_grad_any(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_y,
+                            const double *d_yerr, double *logdet, double *ydota, double *grad);
+int tgp_gp_solve_grad_batch_any(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+                                const double *X, const double *y, const double *yerr,
+                                double *logdet, double *ydota, double *grad, int32_t *info);
+
 /* ---- S4: binned scalar pair correlation, exact binning -----------------------------------
  * w == NULL: unit weights.  TwoD: nbins x nbins pixels over [-max_sep, max_sep]^2, outputs
  * of length nbins^2 (flat index iy*nbins+ix).  Log: nbins log-spaced bins in

@@ -336,19 +336,23 @@ __global__ __launch_bounds__(256, 2) void bkinv_syrk_kernel(double *C, const dou
     post_syrk_tile(C + (int64_t)b * Np * Np, Bt + (int64_t)b * Np * Np, Np, nP, ti, tj, ti >> 1);
 }
 
-// loglik_grad_block for problem b = blockIdx.y: 64 rows (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the
-// lower triangle below n_b, four partial sums per workgroup at partial[(b * nrb * nP + blockIdx.x) * 4]
-__global__ __launch_bounds__(256) void bloglik_grad_kernel(const KParams *__restrict__ kp, const int64_t *__restrict__ ns,
-                                                           const double *__restrict__ X, const double *__restrict__ alpha,
-                                                           const double *__restrict__ C, int64_t Np, GradDims g,
-                                                           double *__restrict__ partial) {
-    const int b = blockIdx.y;
+// loglik_grad_block<KE> for problem b = list[blockIdx.y] (the chunk's problems of evaluator KE, as the K build takes them): 64 rows
+// (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the lower triangle below n_b, four partial sums per workgroup at
+// partial[(b * nrb * nP + blockIdx.x) * 4].  One launch per evaluator present and not one kernel that branches on kp[b].kind:
+// the three bodies in one kernel take the von Karman bodies' 166 VGPRs (3 waves per SIMD) for the Gaussian problems too, whose
+// own body needs 60 (8 waves per SIMD).  A problem's workgroups and sums are the same whichever launch its companions are in.
+template <int KE>
+__global__ __launch_bounds__(256) void bloglik_grad_kernel(const KParams *__restrict__ kp, const int *__restrict__ list,
+                                                           const int64_t *__restrict__ ns, const double *__restrict__ X,
+                                                           const double *__restrict__ alpha, const double *__restrict__ C, int64_t Np,
+                                                           GradDims g, double *__restrict__ partial) {
+    const int b = list[blockIdx.y];
     const int64_t n = ns[b];
     const int64_t pj = blockIdx.x % g.nP, i0 = (int64_t)(blockIdx.x / g.nP) * 64;
     if (i0 >= n || pj * TGP_PW >= n) return;                      // whole workgroups leave together; never summed
     const KParams p = kp[b];
-    loglik_grad_block(p, X + (int64_t)b * 2 * Np, alpha + (int64_t)b * Np, C + (int64_t)b * Np * Np, Np, n, pj, i0,
-                      partial + (((int64_t)b * g.nrb * g.nP) + blockIdx.x) * 4);
+    loglik_grad_block<KE>(p, X + (int64_t)b * 2 * Np, alpha + (int64_t)b * Np, C + (int64_t)b * Np * Np, Np, n, pj, i0,
+                          partial + (((int64_t)b * g.nrb * g.nP) + blockIdx.x) * 4);
 }
 
 // one workgroup per problem: its partial sums (row blocks below n_b x panels below n_b, that order) in a fixed order that depends
@@ -795,18 +799,19 @@ static void batch_subst_identity(hipStream_t st, double *dBt, const BatchBufs &b
 // ---- S2f: the likelihood gradient of every problem of S2e from its factor and alpha, in the same call ---------------------------
 // Per chunk, after batch_factor_chunk with both sweeps: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row
 // tiles, C_b = -Bt_b Bt_b^T over the lower tile pairs, the reduction against dK/dp and one fixed-order sum per problem.
-int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
-                            const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
-    static const char *fn = "tgp_gp_solve_grad_batch";
+// `any`: the entry of seam S2h, which takes the von Karman kinds too (one pair-sum launch per kernel class in the chunk)
+static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+                            const double *X, const double *y, const double *yerr, double *logdet, double *ydota, double *grad,
+                            int32_t *info) {
     if (!ctx) return -1;
     if (!(ks && ns && X && y && logdet && grad && info)) {
-        ctx->err = "tgp_gp_solve_grad_batch: ks, ns, X, y, logdet, grad and info must not be NULL";
+        ctx->err = std::string(fn) + ": ks, ns, X, y, logdet, grad and info must not be NULL";
         return -1;
     }
     BatchRun r;
     int rc = batch_begin(r, ctx, fn, nb, ks, ns, nmax, nullptr, logdet, ydota, info);
     if (rc) return rc;
-    for (int b = 0; b < nb; ++b)
+    for (int b = 0; b < nb && !any; ++b)                    // (an unknown kind has been turned away by batch_begin)
         if (kind_to_ke(ks[b].kind) != KE_GAUSS) {
             ctx->err = std::string(fn) + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks[b].kind) +
                        ": analytic derivatives exist for the Gaussian kernels only (RBF, AnisotropicRBF), as in the reference "
@@ -836,7 +841,11 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
         bgrad_init_kernel<<<dim3((unsigned)(nT * nP), ncn), 256, 0, st>>>(dBt, dC, bb.dns, Np, (int)nP);
         batch_subst_identity(st, dBt, bb, d, ncn);
         bkinv_syrk_kernel<<<dim3((unsigned)(nT * (nT + 1) / 2), ncn), 256, 0, st>>>(dC, dBt, bb.dns, Np, (int)nP);
-        bloglik_grad_kernel<<<dim3((unsigned)(g.nrb * g.nP), ncn), 256, 0, st>>>(bb.dkp, bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
+        const unsigned gw = (unsigned)(g.nrb * g.nP);
+        const int *cnt = bb.cnt, *start = bb.start;         // (all Gaussian: one launch over the identity list, b = blockIdx.y)
+        if (cnt[0]) bloglik_grad_kernel<KE_GAUSS><<<dim3(gw, cnt[0]), 256, 0, st>>>(bb.dkp, bb.dlist + start[0], bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
+        if (cnt[1]) bloglik_grad_kernel<KE_VK><<<dim3(gw, cnt[1]), 256, 0, st>>>(bb.dkp, bb.dlist + start[1], bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
+        if (cnt[2]) bloglik_grad_kernel<KE_AVK><<<dim3(gw, cnt[2]), 256, 0, st>>>(bb.dkp, bb.dlist + start[2], bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
         bloglik_grad_reduce_kernel<<<ncn, 256, 0, st>>>(dpart, bb.dns, g, dgrad);
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[5], st));
@@ -845,6 +854,16 @@ int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const in
     }
     batch_finish(r);
     return 0;
+}
+
+int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                            const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
+    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch", false, nb, ks, ns, nmax, X, y, yerr, logdet, ydota, grad, info);
+}
+
+int tgp_gp_solve_grad_batch_any(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                                const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
+    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch_any", true, nb, ks, ns, nmax, X, y, yerr, logdet, ydota, grad, info);
 }
 
 // ---- S2g: diag(K^-1) of every problem of S2e from its factor, in the same call (leave-one-out, R&W 5.4.2) ----------------------

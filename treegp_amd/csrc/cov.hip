@@ -633,11 +633,12 @@ __global__ __launch_bounds__(256, 2) void kinv_syrk_kernel(double *Cpm, const do
 }
 
 // 64 rows x one 256-column panel per workgroup over the lower triangle; four partial sums per workgroup
+template <int KE>
 __global__ __launch_bounds__(256) void loglik_grad_kernel(KParams p, const double *__restrict__ X, const double *__restrict__ alpha,
                                                           const double *__restrict__ Cpm, int64_t Mp, int64_t n,
                                                           double *__restrict__ partial) {
-    loglik_grad_block(p, X, alpha, Cpm, Mp, n, blockIdx.x, (int64_t)blockIdx.y * 64,
-                      partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
+    loglik_grad_block<KE>(p, X, alpha, Cpm, Mp, n, blockIdx.x, (int64_t)blockIdx.y * 64,
+                          partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 4);
 }
 
 // fixed-order sum of the workgroups' partial sums (one workgroup: the result does not depend on the schedule)
@@ -666,7 +667,12 @@ int launch_loglik_grad(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const d
     const int64_t mt = pl.Mp / TGP_TB;
     kinv_syrk_kernel<<<(unsigned)(mt * (mt + 1) / 2), 256, 0, st>>>(pl.d_C, pl.d_Bt, pl.Mp, pl.nP);
     double *partial = (double *)ctx->scratch2;             // the substitution's staging buffer is free again
-    loglik_grad_kernel<<<dim3((unsigned)pl.nP, (unsigned)nrb), 256, 0, st>>>(make_kparams(k), d_X, d_alpha, pl.d_C, pl.Mp, n, partial);
+    const dim3 grid((unsigned)pl.nP, (unsigned)nrb);
+    switch (kind_to_ke(k->kind)) {                          // the callers have checked the kind
+        case KE_GAUSS: loglik_grad_kernel<KE_GAUSS><<<grid, 256, 0, st>>>(make_kparams(k), d_X, d_alpha, pl.d_C, pl.Mp, n, partial); break;
+        case KE_VK: loglik_grad_kernel<KE_VK><<<grid, 256, 0, st>>>(make_kparams(k), d_X, d_alpha, pl.d_C, pl.Mp, n, partial); break;
+        default: loglik_grad_kernel<KE_AVK><<<grid, 256, 0, st>>>(make_kparams(k), d_X, d_alpha, pl.d_C, pl.Mp, n, partial); break;
+    }
     loglik_grad_reduce_kernel<<<1, 256, 0, st>>>(partial, nparts, partial + nparts * 4);
     TGP_HIP(hipGetLastError());
     TGP_HIP(hipEventRecord(ctx->ev[4], st));
@@ -682,10 +688,14 @@ static int loglik_grad_kind_check(tgp_ctx *ctx, const tgp_kernel *k) {
     return -1;
 }
 
-extern "C" int tgp_gp_loglik_grad(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n, const double *alpha,
-                                  double *grad) {
-    TGP_ARG(f && k && X && alpha && grad && n == f->n);
-    if (loglik_grad_kind_check(ctx, k)) return -1;
+static int loglik_grad_known_kind(tgp_ctx *ctx, const tgp_kernel *k, const char *fn) {
+    if (kind_to_ke(k->kind) >= 0) return 0;
+    ctx->err = std::string(fn) + ": unknown kernel kind " + std::to_string(k->kind);
+    return -1;
+}
+
+static int loglik_grad_from_host(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n, const double *alpha,
+                                 double *grad) {
     TGP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     int rc = tgp_ensure_io(ctx, (size_t)3 * n * sizeof(double));          // coordinates and alpha: outside the scratch areas
@@ -702,12 +712,25 @@ extern "C" int tgp_gp_loglik_grad(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel 
     return 0;
 }
 
+extern "C" int tgp_gp_loglik_grad(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n, const double *alpha,
+                                  double *grad) {
+    TGP_ARG(f && k && X && alpha && grad && n == f->n);
+    if (loglik_grad_kind_check(ctx, k)) return -1;
+    return loglik_grad_from_host(ctx, f, k, X, n, alpha, grad);
+}
+
+// S2h: the same for every kind (the von Karman kinds through loglik_grad_block<KE_VK / KE_AVK>)
+extern "C" int tgp_gp_loglik_grad_any(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n, const double *alpha,
+                                      double *grad) {
+    TGP_ARG(f && k && X && alpha && grad && n == f->n);
+    if (loglik_grad_known_kind(ctx, k, "tgp_gp_loglik_grad_any")) return -1;
+    return loglik_grad_from_host(ctx, f, k, X, n, alpha, grad);
+}
+
 // K build + factorisation + solve + gradient for data that live on the device (tgp_d_gp_solve followed by the above, the
 // factor going back to the context's cache instead of through a handle): one call per evaluation of a gradient-driven fit.
-extern "C" int tgp_d_gp_solve_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_y,
-                                   const double *d_yerr, double *logdet, double *ydota, double *grad) {
-    TGP_ARG(k && d_X && d_y && grad && n > 0);
-    if (loglik_grad_kind_check(ctx, k)) return -1;
+static int d_solve_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_y, const double *d_yerr,
+                        double *logdet, double *ydota, double *grad) {
     TGP_HIP(hipSetDevice(ctx->device));
     int rc = tgp_ensure_io(ctx, (size_t)n * sizeof(double));
     if (rc) return rc;
@@ -720,4 +743,19 @@ extern "C" int tgp_d_gp_solve_grad(tgp_ctx *ctx, const tgp_kernel *k, const doub
     if (!rc && hipEventElapsedTime(&ms, ctx->ev[3], ctx->ev[4]) == hipSuccess) ctx->timings[3] = ms;
     tgp_factor_release_to_cache(ctx, f);
     return rc;
+}
+
+extern "C" int tgp_d_gp_solve_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_y,
+                                   const double *d_yerr, double *logdet, double *ydota, double *grad) {
+    TGP_ARG(k && d_X && d_y && grad && n > 0);
+    if (loglik_grad_kind_check(ctx, k)) return -1;
+    return d_solve_grad(ctx, k, d_X, n, d_y, d_yerr, logdet, ydota, grad);
+}
+
+// S2h: the same for every kind
+extern "C" int tgp_d_gp_solve_grad_any(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_y,
+                                       const double *d_yerr, double *logdet, double *ydota, double *grad) {
+    TGP_ARG(k && d_X && d_y && grad && n > 0);
+    if (loglik_grad_known_kind(ctx, k, "tgp_d_gp_solve_grad_any")) return -1;
+    return d_solve_grad(ctx, k, d_X, n, d_y, d_yerr, logdet, ydota, grad);
 }

@@ -5,6 +5,7 @@
 #pragma once
 #include "tgp_internal.h"
 #include "kernel_eval.h"
+#include "bessel_k16.h"
 #include "gemm_tile.h"
 
 // element (i, j) of a `rows`-row array stored in 256-column panels (panel p at p * rows * 256, ld 256)
@@ -122,11 +123,23 @@ __device__ __forceinline__ double row_sqnorm_wave_from(const double *__restrict_
 }
 
 // The likelihood gradient's pair sum of one workgroup: rows i0 .. i0 + 63 x the 256-column panel pj of the lower triangle
-// below n, against C = -K^-1 (panels of Mp rows); the four partial sums to out[0 .. 3]
+// below n, against C = -K^-1 (panels of Mp rows); the four partial sums to out[0 .. 3].
+// KE_GAUSS: dK/d(a, b, c) = -1/2 K (dx^2, 2 dx dy, dy^2).  KE_VK / KE_AVK (seam S2h): K = amp f(u), u^2 the quadratic form, so
+// dK/d(a, b, c) = amp f'(u) / (2 u) (dx^2, 2 dx dy, dy^2) = -1/2 amp w(u) (...) with w = -f'/u of bessel_k16.h: the Gaussian
+// body with f in slot 0 and w in slots 1 .. 3, both from one u, evaluated as the value kernel evaluates it.  A pair at u == 0
+// off the diagonal counts f = 1 and no slope (w(0) is infinite and is never asked for); beyond the value's cutoff both are 0.
+// The von Karman kinds read both Chebyshev tables from LDS copies made once per workgroup.  `p.kind` is not read.
+template <int KE>
 __device__ __forceinline__ void loglik_grad_block(const KParams &p, const double *__restrict__ X, const double *__restrict__ alpha,
                                                   const double *__restrict__ Cpm, int64_t Mp, int64_t n, int64_t pj, int64_t i0,
                                                   double *__restrict__ out) {
     __shared__ double red[4][4];
+    __shared__ double tab_f[KE == KE_GAUSS ? 1 : 6 * K56_NDEG], tab_w[KE == KE_GAUSS ? 1 : 6 * K16_NDEG];
+    if constexpr (KE != KE_GAUSS) {
+        vonkarman_stage_table(tab_f);
+        vonkarman_slope_stage_table(tab_w);
+        __syncthreads();
+    }
     const int tid = threadIdx.x;
     const int64_t j = pj * TGP_PW + tid;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
@@ -142,11 +155,24 @@ __device__ __forceinline__ void loglik_grad_block(const KParams &p, const double
                 acc[0] += 0.5 * m * p.amp;                          // the pair (i, i) counts once, d K_ii / d log amp = amp
             } else {
                 const double dx = X[2 * i] - xj, dy = X[2 * i + 1] - yj;
-                const double e = p.amp * exp(-0.5 * quad_form(p, dx, dy)) * m;
-                acc[0] += e;
-                acc[1] -= 0.5 * e * dx * dx;
-                acc[2] -= e * dx * dy;
-                acc[3] -= 0.5 * e * dy * dy;
+                if constexpr (KE == KE_GAUSS) {
+                    const double e = p.amp * exp(-0.5 * quad_form(p, dx, dy)) * m;
+                    acc[0] += e;
+                    acc[1] -= 0.5 * e * dx * dx;
+                    acc[2] -= e * dx * dy;
+                    acc[3] -= 0.5 * e * dy * dy;
+                } else {
+                    const double u = (KE == KE_VK) ? sqrt(dx * dx + dy * dy) * p.inv_ell : sqrt(quad_form(p, dx, dy));
+                    if (u == 0.0) {
+                        acc[0] += p.amp * m;                        // coincident points: f = 1, no slope
+                    } else {
+                        acc[0] += p.amp * vonkarman_unit_tab(u, tab_f) * m;
+                        const double g = p.amp * vonkarman_slope_tab(u, tab_w) * m;
+                        acc[1] -= 0.5 * g * dx * dx;
+                        acc[2] -= g * dx * dy;
+                        acc[3] -= 0.5 * g * dy * dy;
+                    }
+                }
             }
         }
     }

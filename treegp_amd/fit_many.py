@@ -10,6 +10,8 @@ per route and releases them:
 
   analytic   Gaussian kernel trees with a ``spec_jacobian``: value and exact gradient of every object from
              ``ops.gp_solve_grad_batch`` (K^-1 formed on the device per problem), chain rule to theta on the host;
+  analytic-vk  on request (``gradient="analytic-vk"``): every kernel ``kernel_to_spec`` describes, the von Karman kinds with
+             the exact derivative of seam S2h (include/tgp.h), from ``ops.gp_solve_grad_batch_any``;
   fd         the other kernels ``kernel_to_spec`` describes (von Karman kinds), or every object with ``gradient="fd"``: SciPy's
              forward differences with ``_FD_STEP`` (log_likelihood.py's scheme, the reference's iterates), the ntheta + 1
              points of every object in one ``ops.gp_solve_batch(want_alpha=False)``.
@@ -52,7 +54,10 @@ class _Fit(object):
         try:
             self.work.theta = theta
             spec = kernel_to_spec(self.work)
-            jac = spec_jacobian(self.work) if self.route == "analytic" else None
+            if self.route == "analytic-vk":
+                jac = spec_jacobian(self.work, von_karman=True)
+            else:
+                jac = spec_jacobian(self.work) if self.route == "analytic" else None
         except (FloatingPointError, ValueError):
             return None
         return spec, jac
@@ -77,14 +82,17 @@ def _log_likelihoods(fits, specs):
 
 def _evaluate(requests):
     """{slot: (fit, theta)} -> {slot: (-log L, -d log L / d theta)}: one ``ops.gp_solve_grad_batch`` for the requests of the
-    analytic route and one ``ops.gp_solve_batch`` for those of the finite-difference route."""
+    analytic route, one ``ops.gp_solve_grad_batch_any`` for those of the analytic-vk route (all four kinds) and one
+    ``ops.gp_solve_batch`` for those of the finite-difference route."""
     out = {}
     exact, exact_fits, exact_specs = [], [], []
+    any_kind = False
     fd, fd_fits, fd_specs = [], [], []
     for slot in sorted(requests):
         fit, theta = requests[slot]
         ntheta = len(theta)
-        if fit.route == "analytic":
+        if fit.route in ("analytic", "analytic-vk"):        # (solve_many gives every fit of a call the same exact route)
+            any_kind = fit.route == "analytic-vk"
             sj = fit.spec_at(theta)
             if sj is None:
                 out[slot] = (np.inf, np.zeros(ntheta))
@@ -106,8 +114,9 @@ def _evaluate(requests):
                 fd_fits.append(fit)
                 fd_specs.append(s[0])
     if exact:
-        log_det, chi2, g4, info = ops.gp_solve_grad_batch(exact_specs, [f.X for f in exact_fits], [f.y for f in exact_fits],
-                                                          [f.y_err for f in exact_fits])
+        solve_grad_batch = ops.gp_solve_grad_batch_any if any_kind else ops.gp_solve_grad_batch
+        log_det, chi2, g4, info = solve_grad_batch(exact_specs, [f.X for f in exact_fits], [f.y for f in exact_fits],
+                                                   [f.y_err for f in exact_fits])
         for k, (slot, jac, ntheta) in enumerate(exact):
             with np.errstate(invalid="ignore", over="ignore"):
                 ll = -0.5 * chi2[k] - exact_fits[k].const - 0.5 * log_det[k]
@@ -205,13 +214,19 @@ def solve_many(gps, gradient="auto"):
 
     ``gradient``: "auto" (default) gives L-BFGS-B the exact gradient for the Gaussian kernels (RBF, AnisotropicRBF) and SciPy's
     forward differences for the von Karman kinds; "fd" forward differences for every object, the reference's iterates;
-    "analytic" raises NotImplementedError for an eligible object whose kernel has no analytic derivative."""
-    if gradient not in ("auto", "fd", "analytic"):
-        raise ValueError("solve_many: gradient must be 'auto', 'fd' or 'analytic', got %r" % (gradient,))
+    "analytic" raises NotImplementedError for an eligible object whose kernel has no analytic derivative; "analytic-vk" gives
+    every eligible object, the von Karman kinds included, the exact gradient (``ops.gp_solve_grad_batch_any``: a derivative the
+    reference does not have), one call per rendezvous."""
+    if gradient not in ("auto", "fd", "analytic", "analytic-vk"):
+        raise ValueError("solve_many: gradient must be 'auto', 'fd', 'analytic' or 'analytic-vk', got %r" % (gradient,))
     gps = list(gps)
     fits, batched = [], set()
     for i, gp in enumerate(gps):
         if gp.optimizer != "log-likelihood" or _batch_spec(gp) is None:
+            continue
+        if gradient == "analytic-vk":                      # every kernel _batch_spec accepts has a derivative there
+            fits.append(_Fit(i, gp, "analytic-vk"))
+            batched.add(i)
             continue
         exact = _has_analytic_gradient(gp.kernel)
         if gradient == "analytic" and not exact:

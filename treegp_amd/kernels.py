@@ -252,19 +252,23 @@ def kernel_to_spec(kernel):
     raise NotImplementedError("kernel %r is not supported by the GPU hot path" % (kernel,))
 
 
-def spec_jacobian(kernel):
+def spec_jacobian(kernel, *, von_karman=False):
     """d(log amp, a, b, c) / d theta, shape (ntheta, 4), for the Gaussian kernel trees ``kernel_to_spec`` accepts
     (theta in scikit-learn's order: a Product's k1 first).  ``ops.gp_loglik_grad`` returns d logL / d(log amp, a, b, c);
     its product with this matrix is d logL / d theta with the kernel derivative of the reference:
     dK/dtheta_k = -1/2 K dX^T (dInvLam/dtheta_k) dX with dInvLam = dL L^T + L dL^T, dL the single-element matrices of
-    ``treegp/kernels.py:138-145`` (AnisotropicRBF), and scikit-learn's own for ConstantKernel (K) and RBF."""
+    ``treegp/kernels.py:138-145`` (AnisotropicRBF), and scikit-learn's own for ConstantKernel (K) and RBF.
+
+    ``von_karman=True`` adds the von Karman classes, for the four numbers of ``ops.gp_loglik_grad_any`` (a derivative the
+    reference does not have: kernels.py:278-288, 383-384): AnisotropicVonKarman has AnisotropicRBF's parametrisation and rows;
+    VonKarman has a = c = l^-2, theta = log l, the row of an isotropic RBF."""
     if isinstance(kernel, Product):
-        return np.vstack([spec_jacobian(kernel.k1), spec_jacobian(kernel.k2)])
+        return np.vstack([spec_jacobian(kernel.k1, von_karman=von_karman), spec_jacobian(kernel.k2, von_karman=von_karman)])
     if isinstance(kernel, ConstantKernel):
         if kernel.hyperparameter_constant_value.fixed:
             return np.zeros((0, 4))
         return np.array([[1.0, 0.0, 0.0, 0.0]])
-    if isinstance(kernel, AnisotropicRBF):
+    if isinstance(kernel, AnisotropicRBF) or (von_karman and isinstance(kernel, AnisotropicVonKarman)):
         if kernel.hyperparameter_cholesky_factor.fixed:         # theta is empty then (kernels.py:128-130)
             return np.zeros((0, 4))
         nd = kernel.ndim
@@ -280,5 +284,10 @@ def spec_jacobian(kernel):
             return np.array([[0.0, -2.0 / ls[0] ** 2, 0.0, -2.0 / ls[0] ** 2]])
         if ls.size == 2:
             return np.array([[0.0, -2.0 / ls[0] ** 2, 0.0, 0.0], [0.0, 0.0, 0.0, -2.0 / ls[1] ** 2]])
+    if von_karman and isinstance(kernel, VonKarman) and not kernel.anisotropic:
+        if kernel.hyperparameter_length_scale.fixed:
+            return np.zeros((0, 4))
+        ell = float(np.ravel(kernel.length_scale)[0])
+        return np.array([[0.0, -2.0 / ell ** 2, 0.0, -2.0 / ell ** 2]])
     raise NotImplementedError("no analytic derivative for %r (the reference has one for AnisotropicRBF only: "
                               "treegp/kernels.py:128-150)" % (kernel,))

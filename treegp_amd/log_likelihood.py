@@ -67,7 +67,8 @@ class log_likelihood(object):
         # the exact gradient instead (log_likelihood_gradient; Gaussian kernels only) -- a different path through theta-space
         # to the same optimum.  "auto" (default): finite differences, the reference's iterates, wherever their ntheta + 1
         # evaluations run side by side (n <= 16 384); above that, where each of them is a full solve of its own, the exact
-        # gradient (1.7 - 2 x a solve instead of ntheta more solves) if the kernel has one.
+        # gradient (1.7 - 2 x a solve instead of ntheta more solves) if the kernel has one.  "analytic-vk": the exact gradient
+        # for all four kinds, the von Karman ones through the derivative the reference does not have (include/tgp.h, S2h).
         self.gradient = os.environ.get("TGP_ML_GRADIENT", "auto")
 
     def log_likelihood(self, kernel, ctx=None, resident=None):
@@ -143,20 +144,24 @@ class log_likelihood(object):
                 out[i] = ll[j] if info[j] == 0 and np.isfinite(ll[j]) else -np.inf
         return out
 
-    def log_likelihood_gradient(self, kernel, ctx=None, resident=None):
+    def log_likelihood_gradient(self, kernel, ctx=None, resident=None, any_kind=False):
         """(log L, d log L / d theta): 1/2 tr((alpha alpha^T - K^-1) dK/dtheta_k) with the kernel derivative of
         ``treegp/kernels.py:128-150``; K^-1 is formed on the device from the factor of the same solve
-        (``ops.gp_loglik_grad``).  Failures give (-inf, zeros) as ``log_likelihood`` gives -inf."""
+        (``ops.gp_loglik_grad``).  Failures give (-inf, zeros) as ``log_likelihood`` gives -inf.
+        ``any_kind=True``: the von Karman kernels too, through the entries of seam S2h (``ops.gp_loglik_grad_any``) and
+        ``spec_jacobian(kernel, von_karman=True)``; the same numbers for the Gaussian ones."""
         ntheta = len(kernel.theta)
         try:
             spec = kernel_to_spec(kernel)
-            jac = spec_jacobian(kernel)
+            jac = spec_jacobian(kernel, von_karman=True) if any_kind else spec_jacobian(kernel)
             if resident is not None:
-                log_det, chi2, g4 = ops.gp_solve_grad_resident(spec, resident, ctx=ctx)
+                solve_grad = ops.gp_solve_grad_resident_any if any_kind else ops.gp_solve_grad_resident
+                log_det, chi2, g4 = solve_grad(spec, resident, ctx=ctx)
             else:
                 alpha, log_det, chi2, factor = ops.gp_solve(spec, self.X, self.y, self.y_err, keep=True, ctx=ctx)
                 try:
-                    g4 = ops.gp_loglik_grad(spec, factor, self.X, alpha, ctx=ctx)
+                    loglik_grad = ops.gp_loglik_grad_any if any_kind else ops.gp_loglik_grad
+                    g4 = loglik_grad(spec, factor, self.X, alpha, ctx=ctx)
                 finally:
                     factor.free(keep_memory=True)          # the next evaluation solves the same size on this context
             ll = -0.5 * chi2 - (0.5 * self.ndata) * np.log(2.0 * np.pi) - 0.5 * log_det
@@ -198,6 +203,14 @@ class log_likelihood(object):
         return fitted
 
     def _use_exact_gradient(self, template):
+        if self.gradient == "analytic-vk":                # the exact gradient for all four kinds (seam S2h), asked for explicitly
+            try:
+                spec_jacobian(template, von_karman=True)
+                kernel_to_spec(template)
+            except NotImplementedError:
+                raise NotImplementedError("TGP_ML_GRADIENT=analytic-vk: %r has no analytic derivative on the device (kernel "
+                                          "trees of kernel_to_spec only)" % (template,))
+            return True
         if self.gradient not in ("analytic", "auto"):
             return False
         try:
@@ -241,10 +254,13 @@ class log_likelihood(object):
                 work.theta = theta
                 if state["exact"]:
                     try:
-                        ll, grad = self.log_likelihood_gradient(work, resident=resident)
+                        if self.gradient == "analytic-vk":
+                            ll, grad = self.log_likelihood_gradient(work, resident=resident, any_kind=True)
+                        else:
+                            ll, grad = self.log_likelihood_gradient(work, resident=resident)
                         return -ll, -grad
                     except ops._lib.TgpError as err:
-                        if self.gradient == "analytic":
+                        if self.gradient in ("analytic", "analytic-vk"):
                             raise                         # asked for explicitly: fail loudly
                         import warnings
                         warnings.warn("exact likelihood gradient unavailable (%s); continuing with finite differences" % err)

@@ -206,6 +206,31 @@ def gp_solve_grad_batch(specs, Xs, ys, y_errs=None, ctx=None):
     return logdet, chi2, g4, info.astype(np.int64)
 
 
+def gp_solve_grad_batch_any(specs, Xs, ys, y_errs=None, ctx=None):
+    """``gp_solve_grad_batch`` for all four kernel kinds, mixed freely within the call (tgp_gp_solve_grad_batch_any, seam S2h of
+    include/tgp.h): for the von Karman kinds the exact derivative the reference does not have.  Same arguments and returns; for
+    the Gaussian kinds the same bits."""
+    specs = list(specs)
+    ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("gp_solve_grad_batch_any: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("gp_solve_grad_batch_any: problems of order up to %d, got %d (use gp_solve and gp_loglik_grad_any)"
+                         % (BATCH_NMAX, nmax))
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    logdet = np.empty(nb)
+    chi2 = np.empty(nb)
+    g4 = np.empty((nb, 4))
+    info = np.zeros(nb, dtype=np.int32)
+    rc = lib.tgp_gp_solve_grad_batch_any(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(logdet),
+                                         ptr(chi2), ptr(g4), ptr(info))
+    check(ctx, rc, "tgp_gp_solve_grad_batch_any")
+    return logdet, chi2, g4, info.astype(np.int64)
+
+
 def gp_loo_batch(specs, Xs, ys, y_errs=None, ctx=None):
     """gp_solve_batch plus, from each problem's factor in the same call, d_b = diag((K_b + diag(y_err_b^2))^-1)
     (tgp_gp_loo_batch): with alpha, all that the leave-one-out quantities of a GP need (treegp_amd.loo).  Arguments as
@@ -470,6 +495,20 @@ def gp_solve_grad_resident(spec, problem, ctx=None):
     return logdet.value, ydota.value, grad
 
 
+def gp_solve_grad_resident_any(spec, problem, ctx=None):
+    """``gp_solve_grad_resident`` for all four kernel kinds (``tgp_d_gp_solve_grad_any``, seam S2h)."""
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    logdet, ydota = C.c_double(0.0), C.c_double(0.0)
+    grad = np.empty(4)
+    rc = lib.tgp_d_gp_solve_grad_any(ctx, C.byref(spec.to_c()), problem.d_X, problem.n, problem.d_y, problem.d_e,
+                                     C.byref(logdet), C.byref(ydota), ptr(grad))
+    check(ctx, rc, "tgp_d_gp_solve_grad_any")
+    if rc > 0:
+        raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % rc)
+    return logdet.value, ydota.value, grad
+
+
 def gp_predict(spec, X, alpha, Xs, ctx=None):
     """ys = k(Xs, X) @ alpha without materialising the cross kernel (gp_interp.py:177,183)."""
     eng = _dist_engine(len(X), ctx)
@@ -536,6 +575,20 @@ def gp_loglik_grad(spec, factor, X, alpha, ctx=None):
     grad = np.empty(4)
     rc = lib.tgp_gp_loglik_grad(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(grad))
     check(ctx, rc, "tgp_gp_loglik_grad")
+    return grad
+
+
+def gp_loglik_grad_any(spec, factor, X, alpha, ctx=None):
+    """``gp_loglik_grad`` for all four kernel kinds (``tgp_gp_loglik_grad_any``, seam S2h): for the von Karman kinds the sums
+    with the profile f in slot 0 and w = -f'/u in slots 1 .. 3; ``kernels.spec_jacobian(kernel, von_karman=True)`` maps the four
+    numbers to d logL / d theta.  The same bits as ``gp_loglik_grad`` for the Gaussian kinds."""
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    X2 = as_xy(X)
+    alpha = f64(alpha)
+    grad = np.empty(4)
+    rc = lib.tgp_gp_loglik_grad_any(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(grad))
+    check(ctx, rc, "tgp_gp_loglik_grad_any")
     return grad
 
 
