@@ -9,6 +9,7 @@
  *   S2e many small S2 at once           treegp/gp_interp.py:180-182, treegp/log_likelihood.py:29-33, 43-62, README.rst:28
  *   S2f many small S2 + S2d at once     treegp/log_likelihood.py:43-62 for the problems of S2e (one evaluation of many fits)
  *   S2g many small S2 + diag(K^-1)      not in the reference: leave-one-out for the problems of S2e (R&W 5.4.2)
+ *   S1s / S2s  S1, S2, S3 .. S3c for sums of kernels   treegp/kernels.py:17-59 (eval_kernel evals any tree)
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
@@ -314,6 +315,46 @@ int tgp_d_gp_solve_grad_any(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X
 int tgp_gp_solve_grad_batch_any(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
                                 const double *X, const double *y, const double *yerr,
                                 double *logdet, double *ydota, double *grad, int32_t *info);
+
+/* ---- S1s / S2s: sums of 2 .. TGP_SUM_MAX parametrised kernels, evaluated on the device ------------------------------------------
+ * The reference knows sums only through treegp/kernels.py:17-59: eval_kernel evals ANY scikit-learn tree, e.g.
+ * "0.3**2 * AnisotropicVonKarman(...) + 0.5**2 * AnisotropicRBF(...)", and gp_interp.py:177-192 works with the n x n (and M x n)
+ * matrices that kernel(X1[, X2]) returns on the host.  Here the n x n matrix never visits the host: the kernels that STORE kernel
+ * values (packed K build, cross panels of the posterior, dense kernel matrix) evaluate every term in registers and store the sum
+ * once; everything that only consumes kernel values is linear in the kernel and runs the single-kernel launches once per term.
+ * Rounding: an off-diagonal element is ((v_0 + v_1) + v_2) + v_3, plain fp64 adds in term order, v_t carrying exactly the bits the
+ * single-kernel entry writes for term t (the amplitude multiply is rounded before the add); the diagonal of a self matrix is
+ * ((amp_0 + amp_1) + ...) exactly, plus yerr_i^2 in the K build.  With nterms == 1 every entry IS its namesake: the same bits.
+ * Each entry mirrors its namesake's arguments, limits, return codes and timings with a tgp_kernel_sum in place of the tgp_kernel;
+ * nterms < 1, nterms > TGP_SUM_MAX or an unknown kind in any term returns -1 with a message naming the entry, before anything
+ * runs on the device.  A factor kept by tgp_gp_solve_sum is an ordinary tgp_factor: tgp_factor_solve, _lmul, _inv_diag and
+ * _inv_blocks serve it unchanged.
+ * tgp_gp_predict_sum / tgp_gp_predict_grad_sum: the per-term results of S3 / S3g against the same alpha, added on the device in term
+ * order (bit for bit the host sum of the namesakes' outputs).  tgp_gp_loglik_grad_sum: grad is (nterms, 4) row-major, row t =
+ * d log L / d (log amp_t, a_t, b_t, c_t) in the convention of S2h; K^-1 is formed once and the pair pass of S2h runs once per
+ * term (row t is bit for bit tgp_gp_loglik_grad_any of term t with the same factor and alpha).                                */
+#define TGP_SUM_MAX 4
+typedef struct {
+    int32_t nterms;
+    int32_t _pad;
+    tgp_kernel term[TGP_SUM_MAX];
+} tgp_kernel_sum;
+int tgp_kernel_matrix_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *Y, int64_t m,
+                          double *out);
+int tgp_d_kbuild_lower_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *d_X, int64_t n, const double *d_yerr,
+                           double *d_A);
+int tgp_gp_solve_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *y, const double *yerr,
+                     double *alpha, double *logdet, double *ydota, tgp_factor **keep);
+int tgp_gp_predict_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *alpha,
+                       const double *Xs, int64_t m, double *ys);
+int tgp_gp_predict_grad_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *alpha,
+                            const double *Xs, int64_t m, double *gs);
+int tgp_gp_predict_cov_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                           const double *Xs, int64_t m, double *cov);
+int tgp_gp_predict_var_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                           const double *Xs, int64_t m, double *var);
+int tgp_gp_loglik_grad_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                           const double *alpha, double *grad /* nterms x 4 */);
 
 /* ---- S4: binned scalar pair correlation, exact binning -----------------------------------
  * w == NULL: unit weights.  TwoD: nbins x nbins pixels over [-max_sep, max_sep]^2, outputs

@@ -21,6 +21,13 @@ class TgpKernel(C.Structure):
                 ("b", C.c_double), ("c", C.c_double), ("ell", C.c_double)]
 
 
+TGP_SUM_MAX = 4
+
+
+class TgpKernelSum(C.Structure):
+    _fields_ = [("nterms", C.c_int32), ("_pad", C.c_int32), ("term", TgpKernel * TGP_SUM_MAX)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -87,6 +94,15 @@ SIGNATURES = {
     "tgp_gp_loglik_grad_any": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp]),
     "tgp_d_gp_solve_grad_any": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _dp, _dp, _vp]),
     "tgp_gp_solve_grad_batch_any": (C.c_int, [_vp, C.c_int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # seams S1s / S2s: sums of kernels, each entry its namesake's prototype with a tgp_kernel_sum
+    "tgp_kernel_matrix_sum": (C.c_int, [_vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
+    "tgp_d_kbuild_lower_sum": (C.c_int, [_vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp]),
+    "tgp_gp_solve_sum": (C.c_int, [_vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _dp, _dp, C.POINTER(_vp)]),
+    "tgp_gp_predict_sum": (C.c_int, [_vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tgp_gp_predict_grad_sum": (C.c_int, [_vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tgp_gp_predict_cov_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
+    "tgp_gp_predict_var_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
+    "tgp_gp_loglik_grad_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp]),
     "tgp_d_unpack_lower":(C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "tgp_factor_device": (C.c_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64)]),
     "tgp_debug_syrk_loop": (C.c_int, [_vp, _vp, _i64, C.c_int, _dp, _dp]),

@@ -870,4 +870,114 @@ int tgp_kernel_matrix(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_
     return 0;
 }
 
+// ---- S1s / S2s: the solve and the mean for sums of kernels (kernels and launchers: ksum.hip) -------------------------------
+// tgp_gp_solve with the sum's K build in place of the single kernel's; what follows the build is factor_and_solve either way.
+static int gp_solve_sum_once(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *d_X, int64_t n, const double *d_y,
+                             const double *d_yerr, double *d_alpha, double *logdet, double *ydota, tgp_factor **keep) {
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t Np = padded_n(n);
+    int rc = ensure_factor_cache(ctx, Np);
+    if (rc) return rc;
+    double *d_A = ext_of(ctx)->A_cache;
+    rc = tgp_ensure_scratch(ctx, (size_t)Np * sizeof(double));
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    rc = launch_kbuild_lower_sum(ctx, k, d_X, n, Np, d_yerr, d_A);
+    if (rc) return rc;
+    static const bool no_augment = getenv("TGP_NO_AUGMENT") != nullptr || getenv("TGP_CHI2_BOTH_SWEEPS") != nullptr;
+    static const bool no_augment_alpha = getenv("TGP_NO_AUGMENT_ALPHA") != nullptr;
+    int S_unused = 0;
+    const bool augmented = !no_augment && keep == nullptr && n < Np &&
+                           (d_alpha == nullptr || (!no_augment_alpha && potrs_big_step(Np, &S_unused)));   // as gp_solve_once
+    if (augmented) {
+        rc = launch_augment_rhs(ctx, d_A, Np, n, d_y);
+        if (rc) return rc;
+    }
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    return factor_and_solve(ctx, n, Np, d_y, d_alpha, logdet, ydota, keep, augmented);
+}
+
+int tgp_gp_solve_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *y, const double *yerr,
+                     double *alpha, double *logdet, double *ydota, tgp_factor **keep) {
+    if (tgp_ksum_check(ctx, k, "tgp_gp_solve_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_solve(ctx, &k->term[0], X, n, y, yerr, alpha, logdet, ydota, keep);
+    TGP_ARG(X && y && n > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    int rc = ensure_io(ctx, rup(2 * n * 8) + 3 * rup(n * 8));
+    if (rc) return rc;
+    rc = ensure_hio(ctx, rup(2 * n * 8) + 3 * rup(n * 8));
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_X = ar.take<double>(2 * n), *d_y = ar.take<double>(n), *d_e = ar.take<double>(n), *d_a = ar.take<double>(n);
+    TGP_HIP(h2d(ctx, d_X, X, 2 * n * 8));
+    TGP_HIP(h2d(ctx, d_y, y, n * 8));
+    if (yerr) TGP_HIP(h2d(ctx, d_e, yerr, n * 8));
+    {
+        SolveInFlight here;                                  // as tgp_d_gp_solve: in-kernel hand-offs only for a solve that is alone
+        ctx->mid_allowed = here.alone ? 1 : 0;
+        rc = gp_solve_sum_once(ctx, k, d_X, n, d_y, yerr ? d_e : nullptr, alpha ? d_a : nullptr, logdet, ydota, keep);
+        ctx->mid_allowed = 0;
+        if (rc == TGP_RC_HANDOFF && !ctx->mid_off) {
+            ctx->mid_off = 1;
+            rc = gp_solve_sum_once(ctx, k, d_X, n, d_y, yerr ? d_e : nullptr, alpha ? d_a : nullptr, logdet, ydota, keep);
+        }
+    }
+    if (rc) return rc;
+    if (alpha) TGP_HIP(d2h_sync(ctx, alpha, d_a, n * 8));
+    return 0;
+}
+
+// The mean and its gradient are linear in the kernel: the single-kernel launch sequences once per term against the same alpha
+// (the Gaussian fast paths keep serving Gaussian terms), each into a slot of its own, then one add in term order.
+// width = 1: tgp_gp_predict, 2: tgp_gp_predict_grad.
+static int predict_sum_from_host(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *alpha,
+                                 const double *Xs, int64_t m, int width, double *out) {
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t ob = rup((size_t)width * m * 8);
+    const size_t io_bytes = rup(2 * n * 8) + rup(n * 8) + rup(2 * m * 8) + (size_t)(k->nterms + 1) * ob;
+    int rc = ensure_io(ctx, io_bytes);
+    if (rc) return rc;
+    rc = ensure_hio(ctx, io_bytes);
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_X = ar.take<double>(2 * n), *d_a = ar.take<double>(n), *d_Xs = ar.take<double>(2 * m),
+           *d_out = ar.take<double>((size_t)width * m), *d_T = ar.take<double>((size_t)k->nterms * (ob / 8));
+    TGP_HIP(h2d(ctx, d_X, X, 2 * n * 8));
+    TGP_HIP(h2d(ctx, d_a, alpha, n * 8));
+    TGP_HIP(h2d(ctx, d_Xs, Xs, 2 * m * 8));
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    for (int t = 0; t < k->nterms; ++t) {
+        double *d_t = d_T + (size_t)t * (ob / 8);
+        rc = width == 1 ? launch_predict(ctx, &k->term[t], d_X, n, d_a, d_Xs, m, d_t)
+                        : launch_predict_grad(ctx, &k->term[t], d_X, n, d_a, d_Xs, m, d_t);
+        if (rc) return rc;
+    }
+    rc = launch_sum_terms(ctx, d_T, k->nterms, (int64_t)(ob / 8), (int64_t)width * m, d_out);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    TGP_HIP(d2h_sync(ctx, out, d_out, (size_t)width * m * 8));
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->timings[3] = ms;
+    return 0;
+}
+
+int tgp_gp_predict_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *alpha,
+                       const double *Xs, int64_t m, double *ys) {
+    if (tgp_ksum_check(ctx, k, "tgp_gp_predict_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_predict(ctx, &k->term[0], X, n, alpha, Xs, m, ys);
+    TGP_ARG(X && alpha && Xs && ys && n > 0 && m > 0);
+    return predict_sum_from_host(ctx, k, X, n, alpha, Xs, m, 1, ys);
+}
+
+int tgp_gp_predict_grad_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *X, int64_t n, const double *alpha,
+                            const double *Xs, int64_t m, double *gs) {
+    if (tgp_ksum_check(ctx, k, "tgp_gp_predict_grad_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_predict_grad(ctx, &k->term[0], X, n, alpha, Xs, m, gs);
+    TGP_ARG(X && alpha && Xs && gs && n > 0 && m > 0);
+    return predict_sum_from_host(ctx, k, X, n, alpha, Xs, m, 2, gs);
+}
+
 }  // extern "C"

@@ -759,3 +759,110 @@ extern "C" int tgp_d_gp_solve_grad_any(tgp_ctx *ctx, const tgp_kernel *k, const 
     if (loglik_grad_known_kind(ctx, k, "tgp_d_gp_solve_grad_any")) return -1;
     return d_solve_grad(ctx, k, d_X, n, d_y, d_yerr, logdet, ydota, grad);
 }
+
+// ---- S1s / S2s: the posterior and the likelihood gradient for sums of kernels ------------------------------------------------
+// Covariance and variance differ from their namesakes in the cross panels alone (ksum.hip: every term evaluated in registers,
+// one store per element); k(x_i, x_i) is the sum of the amplitudes.  With one term the namesake itself runs.
+extern "C" int tgp_gp_predict_cov_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                                      const double *Xs, int64_t m, double *cov) {
+    if (tgp_ksum_check(ctx, k, "tgp_gp_predict_cov_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_predict_cov(ctx, f, &k->term[0], X, n, Xs, m, cov);
+    TGP_ARG(f && X && Xs && cov && m > 0 && n == f->n);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    CovPlan pl;
+    int rc = cov_plan(ctx, f, m, true, &pl);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(pl.d_X, X, 2 * n * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(pl.d_Xs, Xs, 2 * m * 8, hipMemcpyHostToDevice, st));
+    rc = launch_cross_panels_sum(ctx, k, pl.d_Xs, m, pl.d_X, n, 0, pl.d_Bt, pl.Mp, pl.Np);
+    if (rc) return rc;
+    rc = launch_cross_panels_sum(ctx, k, pl.d_Xs, m, pl.d_Xs, m, 1, pl.d_C, pl.Mp, pl.Mp);
+    if (rc) return rc;
+    return cov_finish(ctx, f, pl, cov);
+}
+
+extern "C" int tgp_gp_predict_var_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                                      const double *Xs, int64_t m, double *var) {
+    if (tgp_ksum_check(ctx, k, "tgp_gp_predict_var_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_predict_var(ctx, f, &k->term[0], X, n, Xs, m, var);
+    TGP_ARG(f && X && Xs && var && m > 0 && n == f->n);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int64_t Mc = 0;
+    int rc = var_chunk_rows(ctx, f, m, &Mc);
+    if (rc) return rc;
+    CovPlan pl;
+    rc = cov_plan(ctx, f, m, true, &pl, Mc);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(pl.d_X, X, 2 * n * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(pl.d_Xs, Xs, 2 * m * 8, hipMemcpyHostToDevice, st));
+    return var_chunks(ctx, f, pl, Mc, tgp_ksum_amp(k), false, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows, int) {
+        return launch_cross_panels_sum(ctx, k, cp.d_Xs + 2 * r0, rows, cp.d_X, n, 0, cp.d_Bt, cp.Mp, cp.Np);
+    });
+}
+
+// 1/2 tr((alpha alpha^T - K^-1) dK/dp) is a sum over the terms: K^-1 is formed once from the factor, exactly as
+// launch_loglik_grad forms it, and that function's pair pass and fixed-order reduction run once per term on the same -K^-1.
+// Term t's partial sums and result live in a slot of their own in scratch2; grad (host) receives nterms x 4 numbers.
+static int launch_loglik_grad_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *d_X, const double *d_alpha,
+                                  double *grad) {
+    hipStream_t st = ctx->stream;
+    const int64_t n = f->n;
+    CovPlan pl;
+    int rc = cov_plan(ctx, f, n, false, &pl);             // m = n: d_Bt (Np x Np) <- L^-T, d_C (Np x Np) <- -K^-1
+    if (rc) return rc;
+    const int64_t nrb = (n + 63) / 64;
+    const int64_t nparts = nrb * pl.nP;
+    const size_t slot = (size_t)(nparts * 4 + 4);          // doubles per term: the partial sums, then the four results
+    const size_t need = (size_t)k->nterms * slot * sizeof(double), stage = (size_t)pl.Mp * 1024 * sizeof(double);
+    rc = tgp_ensure_scratch2(ctx, need > stage ? need : stage);
+    if (rc) return rc;
+    TGP_HIP(hipMemsetAsync(pl.d_Bt, 0, (size_t)pl.Mp * pl.Np * 8, st));
+    TGP_HIP(hipMemsetAsync(pl.d_C, 0, (size_t)pl.Mp * pl.Mp * 8, st));
+    ident_panels_kernel<<<(unsigned)(pl.Np / 256), 256, 0, st>>>(pl.d_Bt, pl.Mp, pl.Np);
+    rc = cov_substitute(ctx, f, pl, true);
+    if (rc) return rc;
+    const int64_t mt = pl.Mp / TGP_TB;
+    kinv_syrk_kernel<<<(unsigned)(mt * (mt + 1) / 2), 256, 0, st>>>(pl.d_C, pl.d_Bt, pl.Mp, pl.nP);
+    const dim3 grid((unsigned)pl.nP, (unsigned)nrb);
+    for (int t = 0; t < k->nterms; ++t) {
+        double *partial = (double *)ctx->scratch2 + (size_t)t * slot;     // the substitution's staging buffer is free again
+        const tgp_kernel *kt = &k->term[t];
+        switch (kind_to_ke(kt->kind)) {                     // the caller has checked the kinds
+            case KE_GAUSS: loglik_grad_kernel<KE_GAUSS><<<grid, 256, 0, st>>>(make_kparams(kt), d_X, d_alpha, pl.d_C, pl.Mp, n, partial); break;
+            case KE_VK: loglik_grad_kernel<KE_VK><<<grid, 256, 0, st>>>(make_kparams(kt), d_X, d_alpha, pl.d_C, pl.Mp, n, partial); break;
+            default: loglik_grad_kernel<KE_AVK><<<grid, 256, 0, st>>>(make_kparams(kt), d_X, d_alpha, pl.d_C, pl.Mp, n, partial); break;
+        }
+        loglik_grad_reduce_kernel<<<1, 256, 0, st>>>(partial, nparts, partial + nparts * 4);
+    }
+    TGP_HIP(hipGetLastError());
+    TGP_HIP(hipEventRecord(ctx->ev[4], st));
+    TGP_HIP(hipMemcpy2DAsync(grad, 4 * sizeof(double), (double *)ctx->scratch2 + nparts * 4, slot * sizeof(double), 4 * sizeof(double),
+                             (size_t)k->nterms, hipMemcpyDeviceToHost, st));
+    TGP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int tgp_gp_loglik_grad_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                                      const double *alpha, double *grad) {
+    if (tgp_ksum_check(ctx, k, "tgp_gp_loglik_grad_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_loglik_grad_any(ctx, f, &k->term[0], X, n, alpha, grad);
+    TGP_ARG(f && X && alpha && grad && n == f->n);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = tgp_ensure_io(ctx, (size_t)3 * n * sizeof(double));          // coordinates and alpha: outside the scratch areas
+    if (rc) return rc;
+    double *d_X = (double *)tgp_io_buffer(ctx), *d_alpha = d_X + 2 * n;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(d_X, X, 2 * n * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(d_alpha, alpha, n * 8, hipMemcpyHostToDevice, st));
+    rc = launch_loglik_grad_sum(ctx, f, k, d_X, d_alpha, grad);
+    if (rc) return rc;
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[4]));
+    ctx->timings[3] = ms;
+    return 0;
+}

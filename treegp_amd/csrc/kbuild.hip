@@ -27,21 +27,7 @@ __global__ __launch_bounds__(256) void kbuild_lower_kernel(KParams p, const doub
 // rows is not part of the factor and is not written.  Gaussian kernels take their exponent pre-scaled by 0.5 log2 e and
 // 2^-s from a range-check-free polynomial (17 fp64 instructions instead of libm's ~30; <= 1 ulp): with one transcendental
 // per 8 bytes stored the first-generation kernel was as much VALU- as HBM-bound (2.2 ms of issue at N = 65 536).
-template <int KE>
-__device__ __forceinline__ double kb_value(const KParams &p, double dx, double dy, const double *tab) {
-    if constexpr (KE == KE_GAUSS) return p.amp * tgp_exp2_neg(quad_form(p, dx, dy));   // p.a, p.b2, p.c pre-scaled by the host
-    else return kernel_value_tab<KE>(p, dx, dy, tab);                                   // von Karman: Chebyshev table in LDS
-}
-
-__device__ __forceinline__ void kb_store(double *dst, const double2 &v) {
-#ifdef TGP_KBUILD_NT
-    __builtin_nontemporal_store(v.x, dst);
-    __builtin_nontemporal_store(v.y, dst + 1);
-#else
-    *reinterpret_cast<double2 *>(dst) = v;
-#endif
-}
-
+// (kb_value / kb_store live in kbuild_tile.h: the slab build of sums, ksum.hip, evaluates and stores with them too.)
 template <int KE>
 __global__ __launch_bounds__(256) void kbuild_slab_kernel(KParams p, const double *__restrict__ X, int64_t n, int64_t Np,
                                                           const double *__restrict__ yerr, double *__restrict__ A) {

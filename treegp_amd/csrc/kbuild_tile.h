@@ -3,6 +3,22 @@
 #include "tgp_internal.h"
 #include "kernel_eval.h"
 
+// Value and store of the slab builds (kbuild.hip: kbuild_slab_kernel; ksum.hip: the same slabs for sums of kernels).
+template <int KE>
+__device__ __forceinline__ double kb_value(const KParams &p, double dx, double dy, const double *tab) {
+    if constexpr (KE == KE_GAUSS) return p.amp * tgp_exp2_neg(quad_form(p, dx, dy));   // p.a, p.b2, p.c pre-scaled by the host
+    else return kernel_value_tab<KE>(p, dx, dy, tab);                                   // von Karman: Chebyshev table in LDS
+}
+
+__device__ __forceinline__ void kb_store(double *dst, const double2 &v) {
+#ifdef TGP_KBUILD_NT
+    __builtin_nontemporal_store(v.x, dst);
+    __builtin_nontemporal_store(v.y, dst + 1);
+#else
+    *reinterpret_cast<double2 *>(dst) = v;
+#endif
+}
+
 // One 128x128 tile per workgroup of 256 threads.  Lane l of wave w owns columns 2l, 2l+1 and
 // rows w, w+4, ... of the tile, so each wave-instruction stores one full 1 KiB row segment.
 // (ti, tj) are GLOBAL 128-tile coordinates; `tile` is where the tile lives (ld 256).

@@ -201,6 +201,18 @@ int launch_kbuild_lower(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, in
                         const double *d_yerr, double *d_A);
 int launch_kernel_dense(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n,
                         const double *d_Y, int64_t m, int self, double *d_out);
+// ksum.hip: sums of parametrised kernels (seams S1s / S2s).  tgp_ksum_check: -1 with a message naming `fn` for a bad term count or
+// an unknown kind; tgp_ksum_amp: ((amp_0 + amp_1) + ...), the diagonal of a self matrix.  The launchers expect a checked sum.
+int tgp_ksum_check(tgp_ctx *ctx, const tgp_kernel_sum *k, const char *fn);
+double tgp_ksum_amp(const tgp_kernel_sum *k);
+int launch_kbuild_lower_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *d_X, int64_t n, int64_t Np,
+                            const double *d_yerr, double *d_A);
+int launch_kernel_dense_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *d_X, int64_t n, const double *d_Y,
+                            int64_t m, int self, double *d_out);
+int launch_cross_panels_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double *d_Xs, int64_t m, const double *d_X, int64_t n,
+                            int self, double *d_out, int64_t rows, int64_t ncols);
+// d_out[i] = ((T[0][i] + T[1][i]) + ...), i < count, over nterms arrays `stride` doubles apart
+int launch_sum_terms(tgp_ctx *ctx, const double *d_T, int nterms, int64_t stride, int64_t count, double *d_out);
 int launch_potrf(tgp_ctx *ctx, double *d_A, int64_t Np, double *d_W, bool defer_info = false, int64_t n_data = -1);
 int tgp_potrf_info_rc(tgp_ctx *ctx, int info);      // device `info` word -> return code (TGP_RC_HANDOFF: in-kernel hand-off timed out)
 #define TGP_RC_HANDOFF (-4)

@@ -12,6 +12,7 @@ import copy
 import numpy as np
 from sklearn.neighbors import KNeighborsRegressor
 
+from . import kernels as _kernels
 from . import ops
 from .fits_io import read_bintable_row
 from .kernels import eval_kernel, kernel_to_spec
@@ -107,11 +108,21 @@ class GPInterpolation(object):
             self._factor.free(keep_memory=True)        # a refit of this object solves the same size next: its memory is reused
         self._factor, self._factor_key = factor, key
 
+    def _device_spec(self, kernel, n=None):
+        """The device description of ``kernel`` for the single-problem routes: ``kernel_to_spec``'s, or else a sum's
+        (``kernels.device_spec``: 2 .. 4 parametrised terms, ``ops.KernelSumSpec``); NotImplementedError for every other
+        tree, which takes the dense route.  The multi-GPU engine has no sum-aware K build: while it would take a problem of
+        ``n`` points (this object's backend included), sums keep the dense route too."""
+        with self._scope():
+            multi_gpu = ops._dist_engine(len(self._X) if n is None else n, None) is not None
+        return _kernels.device_spec(kernel, allow_sum=not multi_gpu, single=kernel_to_spec)
+
     @staticmethod
     def _factor_fingerprint(spec, X1, y_err):
         import hashlib
         h = hashlib.blake2b(digest_size=16)
-        h.update(np.asarray([spec.kind, spec.amp, spec.a, spec.b, spec.c, spec.ell], dtype=np.float64).tobytes())
+        for term in getattr(spec, "terms", [spec]):          # a sum: every term
+            h.update(np.asarray([term.kind, term.amp, term.a, term.b, term.c, term.ell], dtype=np.float64).tobytes())
         for arr in (X1, y_err):
             arr = np.ascontiguousarray(arr, dtype=np.float64)
             h.update(str(arr.shape).encode())
@@ -176,9 +187,9 @@ class GPInterpolation(object):
         if return_cov and return_var:
             raise ValueError("at most one of return_cov and return_var may be True")
         try:
-            spec = kernel_to_spec(kernel)
+            spec = self._device_spec(kernel, len(X1))
         except NotImplementedError:
-            # any other scikit-learn kernel tree (Sum, WhiteKernel, Matern, ...): the kernel object evaluates itself on
+            # any other scikit-learn kernel tree (WhiteKernel, Matern, sums beyond kernels.kernel_to_sum_spec, ...): the kernel object evaluates itself on
             # the host, exactly as in the reference, and the device factorises what it returns (tgp_gp_solve_dense)
             return self._return_gp_predict_dense(y, X1, X2, kernel, y_err, return_cov, return_var)
         self._ensure_solution(y, X1, kernel, spec, y_err, want_factor=return_cov or return_var)
@@ -210,15 +221,19 @@ class GPInterpolation(object):
         ``_mean`` of ``normalize`` drops out; a KNN mean function is piecewise constant and contributes nothing (its jumps
         between neighbourhoods are not a slope).  A von Karman field has a cusp on every star: the slope reported there is
         zero.  Uses the cached ``_alpha`` under the rules of ``predict`` (solved for on first use, no factor is kept).
-        Kernels of the dense route (anything ``kernel_to_spec`` does not describe) have no device form of their derivative:
-        NotImplementedError.  Runs on one GPU whichever backend solved."""
+        Kernels of the dense route (anything ``kernels.device_spec`` does not describe: one parametrised kernel or a sum of up
+        to four) have no device form of their derivative: NotImplementedError.  Runs on one GPU whichever backend solved."""
         try:
-            spec = kernel_to_spec(self.kernel)
+            spec = _kernels.device_spec(self.kernel, single=kernel_to_spec)
         except NotImplementedError:
             raise NotImplementedError("predict_gradient needs a kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
-                                      "AnisotropicVonKarman, optionally times a constant); got %r" % (self.kernel,))
+                                      "AnisotropicVonKarman, optionally times a constant, or a sum of up to four of those); "
+                                      "got %r" % (self.kernel,))
         with self._scope():
-            self._ensure_solution(self._residual(), self._X, self.kernel, spec, self._y_err, want_factor=False)
+            solve_spec = spec
+            if isinstance(spec, ops.KernelSumSpec) and ops._dist_engine(len(self._X), None) is not None:
+                solve_spec = None                               # a sum under the multi-GPU engine is solved on the dense route
+            self._ensure_solution(self._residual(), self._X, self.kernel, solve_spec, self._y_err, want_factor=False)
         ndim = 1 if np.ndim(X) < 2 else np.shape(X)[1]
         return ops.gp_predict_grad(spec, self._X, self._alpha, X)[:, :ndim]
 
@@ -253,7 +268,7 @@ class GPInterpolation(object):
         means = np.mean(Y - self._spatial_average, axis=1) if self.normalize else np.zeros(len(Y))
         R = Y - means[:, None] - self._spatial_average[None, :]
         try:
-            spec = kernel_to_spec(self.kernel)
+            spec = self._device_spec(self.kernel)
         except NotImplementedError:
             spec = None
         with self._scope():
@@ -282,7 +297,7 @@ class GPInterpolation(object):
         reuses what the other left; any kernel tree works (the dense route keeps a factor as well)."""
         r = self._residual()
         try:
-            spec = kernel_to_spec(self.kernel)
+            spec = self._device_spec(self.kernel)
         except NotImplementedError:
             spec = None
         with self._scope():
@@ -303,7 +318,7 @@ class GPInterpolation(object):
             kernel = kernel.clone_with_theta(theta)
         r = self._residual()
         try:
-            spec = kernel_to_spec(kernel)
+            spec = self._device_spec(kernel)
         except NotImplementedError:
             spec = None
         try:
@@ -334,7 +349,7 @@ class GPInterpolation(object):
         if perm is not None:
             X, r, sigma = X[perm], r[perm], np.asarray(sigma)[perm]
         try:
-            spec = kernel_to_spec(kernel)
+            spec = self._device_spec(kernel)
         except NotImplementedError:
             spec = None
         with self._scope():
@@ -373,7 +388,7 @@ class GPInterpolation(object):
         if perm is None:
             r = self._residual()
             try:
-                spec = kernel_to_spec(self.kernel)
+                spec = self._device_spec(self.kernel)
             except NotImplementedError:
                 spec = None
             with self._scope():
@@ -429,7 +444,7 @@ class GPInterpolation(object):
         means = np.mean(Y - self._spatial_average, axis=1) if self.normalize else np.zeros(len(Y))
         R = Y - means[:, None] - self._spatial_average[None, :]
         try:
-            spec = kernel_to_spec(self.kernel)
+            spec = self._device_spec(self.kernel)
         except NotImplementedError:
             spec = None
         with self._scope():

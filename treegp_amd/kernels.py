@@ -10,7 +10,7 @@ S1) instead of scipy ``pdist/cdist`` + ``special.kv``.  There is no host evaluat
 """
 import numpy as np
 from sklearn.gaussian_process.kernels import (ConstantKernel, Hyperparameter, Kernel, NormalizedKernelMixin,
-                                              Product, RBF, StationaryKernelMixin)
+                                              Product, RBF, StationaryKernelMixin, Sum)
 
 from . import _lib
 from . import ops
@@ -250,6 +250,56 @@ def kernel_to_spec(kernel):
             return ops.KernelSpec(_lib.TGP_RBF, amp=amp, a=1.0 / ls[0] ** 2, b=0.0, c=1.0 / ls[1] ** 2)
         raise NotImplementedError("RBF with %d length scales" % ls.size)
     raise NotImplementedError("kernel %r is not supported by the GPU hot path" % (kernel,))
+
+
+def _sum_leaves(kernel):
+    """the terms of a (nested) scikit-learn Sum in its own order, k1 before k2"""
+    if isinstance(kernel, Sum):
+        return _sum_leaves(kernel.k1) + _sum_leaves(kernel.k2)
+    return [kernel]
+
+
+def kernel_to_sum_spec(kernel):
+    """``ops.KernelSumSpec`` for a (nested) scikit-learn ``Sum`` whose leaves, in scikit-learn's own order (k1 before k2), are
+    2 .. TGP_SUM_MAX trees ``kernel_to_spec`` accepts -- e.g. "0.3**2 * AnisotropicVonKarman(...) + 0.5**2 * AnisotropicRBF(...)".
+    Everything else raises NotImplementedError and keeps the dense route: any tree with a WhiteKernel or a Matern leaf, a
+    constant multiplying a whole sum, more than TGP_SUM_MAX terms.  There is no silent host fallback."""
+    if not isinstance(kernel, Sum):
+        raise NotImplementedError("not a sum of kernels: %r" % (kernel,))
+    leaves = _sum_leaves(kernel)
+    if len(leaves) > _lib.TGP_SUM_MAX:
+        raise NotImplementedError("sums of at most %d kernels run on the GPU, got %d terms in %r"
+                                  % (_lib.TGP_SUM_MAX, len(leaves), kernel))
+    return ops.KernelSumSpec([kernel_to_spec(leaf) for leaf in leaves])
+
+
+def device_spec(kernel, allow_sum=True, single=None):
+    """The device description of a kernel for the single-problem routes: ``kernel_to_spec``'s ``ops.KernelSpec``, or else
+    ``kernel_to_sum_spec``'s ``ops.KernelSumSpec``; NotImplementedError for every other tree (the dense route).
+    ``allow_sum=False``: sums raise too (the multi-GPU engine has no sum-aware K build: they keep the dense route there).
+    ``single``: the caller's own ``kernel_to_spec`` name, so that the modules' call sites keep resolving single kernels
+    through the name they import (their tests stand in for it there)."""
+    try:
+        return (single or kernel_to_spec)(kernel)
+    except NotImplementedError:
+        if not allow_sum:
+            raise
+        return kernel_to_sum_spec(kernel)
+
+
+def sum_spec_jacobian(kernel):
+    """d(log amp_t, a_t, b_t, c_t for every term t) / d theta, shape (ntheta, 4 * nterms), for the sums ``kernel_to_sum_spec``
+    accepts: block structured, the theta of a Sum being k1.theta then k2.theta, term t's rows ``spec_jacobian(term_t,
+    von_karman=True)`` in columns 4 t .. 4 t + 3.  Its product with the flattened ``ops.gp_loglik_grad_sum`` is d logL / d theta."""
+    if not isinstance(kernel, Sum):
+        raise NotImplementedError("not a sum of kernels: %r" % (kernel,))
+    blocks = [spec_jacobian(leaf, von_karman=True) for leaf in _sum_leaves(kernel)]
+    out = np.zeros((sum(len(b) for b in blocks), 4 * len(blocks)))
+    row = 0
+    for t, b in enumerate(blocks):
+        out[row:row + len(b), 4 * t:4 * t + 4] = b
+        row += len(b)
+    return out
 
 
 def spec_jacobian(kernel, *, von_karman=False):

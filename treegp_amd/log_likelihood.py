@@ -20,6 +20,7 @@ import numpy as np
 from scipy import optimize
 
 from . import _lib, ops
+from . import kernels as _kernels
 from ._lib import TgpError
 from .kernels import kernel_to_spec, spec_jacobian
 
@@ -71,18 +72,23 @@ class log_likelihood(object):
         # for all four kinds, the von Karman ones through the derivative the reference does not have (include/tgp.h, S2h).
         self.gradient = os.environ.get("TGP_ML_GRADIENT", "auto")
 
+    def _device_spec(self, kernel):
+        """``kernel_to_spec``'s description, or else a sum's (``kernels.device_spec``) -- except on the multi-GPU route, where
+        sums keep the dense route; NotImplementedError for every other tree"""
+        return _kernels.device_spec(kernel, allow_sum=not self.distributed, single=kernel_to_spec)
+
     def log_likelihood(self, kernel, ctx=None, resident=None):
         """-0.5 y.K^-1.y - (n/2) log 2 pi - 0.5 log det K; any failure (e.g. K not positive
         definite) gives -inf, as at log_likelihood.py:28-39.  `resident`: the data already on the device
         (ops.ResidentProblem, used by optimizer() for the evaluations of one fit)."""
         try:
             try:
-                spec = kernel_to_spec(kernel)
+                spec = self._device_spec(kernel)
             except NotImplementedError:
                 spec = None                       # any other scikit-learn kernel tree: it evaluates itself on the host
             if spec is None:
                 _, log_det, chi2, _ = ops.gp_solve_dense(kernel(self.X), self.y, self.y_err, want_alpha=False, ctx=ctx)
-            elif resident is not None:
+            elif resident is not None and not isinstance(spec, ops.KernelSumSpec):     # (no resident variant of the sum solve)
                 log_det, chi2 = ops.gp_solve_resident(spec, resident, ctx=ctx)
             else:
                 _, log_det, chi2, _ = ops.gp_solve(spec, self.X, self.y, self.y_err, want_alpha=False, ctx=ctx)
@@ -149,12 +155,23 @@ class log_likelihood(object):
         ``treegp/kernels.py:128-150``; K^-1 is formed on the device from the factor of the same solve
         (``ops.gp_loglik_grad``).  Failures give (-inf, zeros) as ``log_likelihood`` gives -inf.
         ``any_kind=True``: the von Karman kernels too, through the entries of seam S2h (``ops.gp_loglik_grad_any``) and
-        ``spec_jacobian(kernel, von_karman=True)``; the same numbers for the Gaussian ones."""
+        ``spec_jacobian(kernel, von_karman=True)``; the same numbers for the Gaussian ones.  With ``any_kind=True`` also the sums
+        of ``kernels.kernel_to_sum_spec``: a kept factor, ``ops.gp_loglik_grad_sum`` and ``kernels.sum_spec_jacobian``."""
         ntheta = len(kernel.theta)
         try:
-            spec = kernel_to_spec(kernel)
-            jac = spec_jacobian(kernel, von_karman=True) if any_kind else spec_jacobian(kernel)
-            if resident is not None:
+            spec = self._device_spec(kernel) if any_kind else kernel_to_spec(kernel)
+            is_sum = isinstance(spec, ops.KernelSumSpec)
+            if is_sum:
+                jac = _kernels.sum_spec_jacobian(kernel)
+            else:
+                jac = spec_jacobian(kernel, von_karman=True) if any_kind else spec_jacobian(kernel)
+            if is_sum:
+                alpha, log_det, chi2, factor = ops.gp_solve(spec, self.X, self.y, self.y_err, keep=True, ctx=ctx)
+                try:
+                    g4 = ops.gp_loglik_grad_sum(spec, factor, self.X, alpha, ctx=ctx).ravel()
+                finally:
+                    factor.free(keep_memory=True)
+            elif resident is not None:
                 solve_grad = ops.gp_solve_grad_resident_any if any_kind else ops.gp_solve_grad_resident
                 log_det, chi2, g4 = solve_grad(spec, resident, ctx=ctx)
             else:
@@ -205,11 +222,13 @@ class log_likelihood(object):
     def _use_exact_gradient(self, template):
         if self.gradient == "analytic-vk":                # the exact gradient for all four kinds (seam S2h), asked for explicitly
             try:
-                spec_jacobian(template, von_karman=True)
-                kernel_to_spec(template)
+                if isinstance(self._device_spec(template), ops.KernelSumSpec):
+                    _kernels.sum_spec_jacobian(template)
+                else:
+                    spec_jacobian(template, von_karman=True)
             except NotImplementedError:
                 raise NotImplementedError("TGP_ML_GRADIENT=analytic-vk: %r has no analytic derivative on the device (kernel "
-                                          "trees of kernel_to_spec only)" % (template,))
+                                          "trees of kernel_to_spec, and sums of them, only)" % (template,))
             return True
         if self.gradient not in ("analytic", "auto"):
             return False

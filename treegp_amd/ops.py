@@ -11,7 +11,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import TgpKernel, check, f64, ptr, as_xy
+from ._lib import TgpKernel, TgpKernelSum, check, f64, ptr, as_xy
 
 
 class KernelSpec(object):
@@ -25,6 +25,46 @@ class KernelSpec(object):
 
     def __repr__(self):
         return "KernelSpec(kind=%d, amp=%r, a=%r, b=%r, c=%r, ell=%r)" % (self.kind, self.amp, self.a, self.b, self.c, self.ell)
+
+
+class KernelSumSpec(object):
+    """A sum of 1 .. ``_lib.TGP_SUM_MAX`` parametrised kernels (a list of ``KernelSpec``, in the order the values are added):
+    what ``treegp_amd.kernels.kernel_to_sum_spec`` derives from a scikit-learn ``Sum`` (2 terms or more; with one term every
+    entry is its single-kernel namesake, bit for bit).  ``kernel_matrix``, ``gp_solve``,
+    ``gp_predict``, ``gp_predict_grad``, ``gp_predict_cov`` and ``gp_predict_var`` take it wherever they take a ``KernelSpec``
+    and go to the ``_sum`` entries of include/tgp.h (seams S1s / S2s); ``gp_loglik_grad_sum`` is its likelihood gradient.
+    The multi-GPU engine does not take sums: these calls run on this process's GPU whatever the multi-GPU settings."""
+    __slots__ = ("terms",)
+
+    def __init__(self, terms):
+        self.terms = list(terms)
+        if not 1 <= len(self.terms) <= _lib.TGP_SUM_MAX:
+            raise ValueError("a kernel sum holds 1 .. %d terms, got %d" % (_lib.TGP_SUM_MAX, len(self.terms)))
+
+    @property
+    def amp(self):
+        """k(x, x): the amplitudes added in term order, the diagonal the device writes"""
+        total = self.terms[0].amp
+        for t in self.terms[1:]:
+            total = total + t.amp
+        return total
+
+    def to_c(self):
+        c = TgpKernelSum()
+        c.nterms = len(self.terms)
+        for i, t in enumerate(self.terms):
+            c.term[i] = t.to_c()
+        return c
+
+    def __repr__(self):
+        return "KernelSumSpec(%r)" % (self.terms,)
+
+
+def _entry(lib, name, spec):
+    """the library entry `name` for a KernelSpec, its `_sum` namesake (same arguments) for a KernelSumSpec"""
+    if isinstance(spec, KernelSumSpec):
+        name += "_sum"
+    return getattr(lib, name), name
 
 
 class Factor(object):
@@ -61,17 +101,18 @@ def kernel_matrix(spec, X, Y=None, ctx=None):
     Replaces kernel.__call__ (treegp/kernels.py:114-126, 249-276, 355-381)."""
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
+    fn, name = _entry(lib, "tgp_kernel_matrix", spec)
     X2 = as_xy(X)
     n = X2.shape[0]
     if Y is None:
         out = np.empty((n, n))
-        rc = lib.tgp_kernel_matrix(ctx, C.byref(spec.to_c()), ptr(X2), n, None, 0, ptr(out))
+        rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), n, None, 0, ptr(out))
     else:
         Y2 = as_xy(Y)
         m = Y2.shape[0]
         out = np.empty((n, m))
-        rc = lib.tgp_kernel_matrix(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(Y2), m, ptr(out))
-    check(ctx, rc, "tgp_kernel_matrix")
+        rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(Y2), m, ptr(out))
+    check(ctx, rc, name)
     return out
 
 
@@ -93,11 +134,12 @@ def gp_solve(spec, X, y, y_err=None, keep=False, want_alpha=True, ctx=None):
     """(alpha, logdet, y.alpha, factor|None) for K = amp k(X) + diag(y_err^2).
     Raises numpy.linalg.LinAlgError when K is not positive definite, as scipy.linalg.cholesky
     does at treegp/gp_interp.py:181."""
-    eng = _dist_engine(len(X), ctx)
+    eng = None if isinstance(spec, KernelSumSpec) else _dist_engine(len(X), ctx)
     if eng is not None:
         return eng.gp_solve(spec, X, y, y_err, keep=keep, want_alpha=want_alpha)
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
+    fn, name = _entry(lib, "tgp_gp_solve", spec)
     X2 = as_xy(X)
     n = X2.shape[0]
     y = f64(y)
@@ -105,9 +147,9 @@ def gp_solve(spec, X, y, y_err=None, keep=False, want_alpha=True, ctx=None):
     alpha = np.empty(n) if want_alpha else None
     logdet, ydota = C.c_double(0.0), C.c_double(0.0)
     h = C.c_void_p()
-    rc = lib.tgp_gp_solve(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(y), ptr(e), ptr(alpha), C.byref(logdet),
-                          C.byref(ydota), C.byref(h) if keep else None)
-    check(ctx, rc, "tgp_gp_solve")
+    rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(y), ptr(e), ptr(alpha), C.byref(logdet),
+            C.byref(ydota), C.byref(h) if keep else None)
+    check(ctx, rc, name)
     if rc > 0:
         raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % rc)
     return alpha, logdet.value, ydota.value, (Factor(ctx, h, n) if keep else None)
@@ -511,7 +553,7 @@ def gp_solve_grad_resident_any(spec, problem, ctx=None):
 
 def gp_predict(spec, X, alpha, Xs, ctx=None):
     """ys = k(Xs, X) @ alpha without materialising the cross kernel (gp_interp.py:177,183)."""
-    eng = _dist_engine(len(X), ctx)
+    eng = None if isinstance(spec, KernelSumSpec) else _dist_engine(len(X), ctx)
     if eng is not None:
         return eng.gp_predict(spec, X, alpha, Xs)
     ctx = ctx or _lib.get_ctx()
@@ -519,8 +561,9 @@ def gp_predict(spec, X, alpha, Xs, ctx=None):
     X2, Xs2 = as_xy(X), as_xy(Xs)
     alpha = f64(alpha)
     ys = np.empty(Xs2.shape[0])
-    rc = lib.tgp_gp_predict(ctx, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(Xs2), Xs2.shape[0], ptr(ys))
-    check(ctx, rc, "tgp_gp_predict")
+    fn, name = _entry(lib, "tgp_gp_predict", spec)
+    rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(Xs2), Xs2.shape[0], ptr(ys))
+    check(ctx, rc, name)
     return ys
 
 
@@ -534,8 +577,9 @@ def gp_predict_grad(spec, X, alpha, Xs, ctx=None):
     X2, Xs2 = as_xy(X), as_xy(Xs)
     alpha = f64(alpha)
     gs = np.empty((Xs2.shape[0], 2))
-    rc = lib.tgp_gp_predict_grad(ctx, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(Xs2), Xs2.shape[0], ptr(gs))
-    check(ctx, rc, "tgp_gp_predict_grad")
+    fn, name = _entry(lib, "tgp_gp_predict_grad", spec)
+    rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(Xs2), Xs2.shape[0], ptr(gs))
+    check(ctx, rc, name)
     return gs
 
 
@@ -546,8 +590,9 @@ def gp_predict_cov(spec, factor, X, Xs, ctx=None):
     X2, Xs2 = as_xy(X), as_xy(Xs)
     m = Xs2.shape[0]
     cov = np.empty((m, m))
-    rc = lib.tgp_gp_predict_cov(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(Xs2), m, ptr(cov))
-    check(ctx, rc, "tgp_gp_predict_cov")
+    fn, name = _entry(lib, "tgp_gp_predict_cov", spec)
+    rc = fn(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(Xs2), m, ptr(cov))
+    check(ctx, rc, name)
     return cov
 
 
@@ -559,8 +604,9 @@ def gp_predict_var(spec, factor, X, Xs, ctx=None):
     X2, Xs2 = as_xy(X), as_xy(Xs)
     m = Xs2.shape[0]
     var = np.empty(m)
-    rc = lib.tgp_gp_predict_var(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(Xs2), m, ptr(var))
-    check(ctx, rc, "tgp_gp_predict_var")
+    fn, name = _entry(lib, "tgp_gp_predict_var", spec)
+    rc = fn(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(Xs2), m, ptr(var))
+    check(ctx, rc, name)
     return var
 
 
@@ -589,6 +635,20 @@ def gp_loglik_grad_any(spec, factor, X, alpha, ctx=None):
     grad = np.empty(4)
     rc = lib.tgp_gp_loglik_grad_any(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(grad))
     check(ctx, rc, "tgp_gp_loglik_grad_any")
+    return grad
+
+
+def gp_loglik_grad_sum(sumspec, factor, X, alpha, ctx=None):
+    """(nterms, 4): row t is ``gp_loglik_grad_any`` of term t -- d log L / d (log amp_t, a_t, b_t, c_t) -- from the factor and
+    alpha of one ``gp_solve(sumspec, ..., keep=True)`` (``tgp_gp_loglik_grad_sum``, seam S2s): K^-1 is formed once, the pair
+    pass runs once per term.  ``kernels.sum_spec_jacobian`` maps the flattened numbers to d logL / d theta."""
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    X2 = as_xy(X)
+    alpha = f64(alpha)
+    grad = np.empty((len(sumspec.terms), 4))
+    rc = lib.tgp_gp_loglik_grad_sum(ctx, factor._h, C.byref(sumspec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(grad))
+    check(ctx, rc, "tgp_gp_loglik_grad_sum")
     return grad
 
 

@@ -16,7 +16,8 @@ from sklearn.gaussian_process.kernels import Exponentiation, KernelOperator
 
 from . import _lib
 from . import ops
-from .kernels import _CholeskyParametrised, eval_kernel, kernel_to_spec
+from . import kernels as _kernels
+from .kernels import _CholeskyParametrised, eval_kernel
 
 
 def check_sampling_args(n_samples, nugget):
@@ -55,9 +56,10 @@ def as_coords(kernel, X):
 
 
 def prior_diag_max(kernel, X):
-    """max over X of k(x, x): amp for the parametrised kernels, max(kernel.diag(X)) for any other kernel tree"""
+    """max over X of k(x, x): amp for the parametrised kernels (the sum of the amplitudes for a sum of them),
+    max(kernel.diag(X)) for any other kernel tree"""
     try:
-        return kernel_to_spec(kernel).amp
+        return _kernels.device_spec(kernel).amp
     except NotImplementedError:
         return float(np.max(kernel.diag(X)))
 
@@ -111,7 +113,7 @@ def gaussian_random_field(kernel, X, n_samples=1, random_state=0, y_err=None, nu
     jitter = nugget * prior_diag_max(kernel, X)
     Z = normals(n_samples, n, random_state)
     try:
-        spec = kernel_to_spec(kernel)
+        spec = _kernels.device_spec(kernel)
     except NotImplementedError:
         spec = None
     if spec is None:
