@@ -12,36 +12,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 
-def _scipy(u, v, val, ue, ve, stat):
-    from scipy.stats import binned_statistic_2d
-    return binned_statistic_2d(u, v, val, bins=[ue, ve], statistic=stat)[0]
-
-
-def _check(u, v, val, ue, ve, err=None):
-    from treegp_amd import ops
-    cnt_ref = _scipy(u, v, val, ue, ve, "count")
-    avg, wrms, cnt = ops.binned_stat_2d(u, v, val, ue, ve, "mean")
-    np.testing.assert_array_equal(cnt, cnt_ref)                               # bin numbers: exact
-    ref = _scipy(u, v, val, ue, ve, "mean")
-    np.testing.assert_array_equal(np.isnan(avg), np.isnan(ref))
-    np.testing.assert_allclose(avg, ref, rtol=1e-13, atol=1e-13 * np.nanmax(np.abs(ref)), equal_nan=True)
-    assert np.all(wrms == 0.0)
-    med, _, cnt2 = ops.binned_stat_2d(u, v, val, ue, ve, "median")
-    np.testing.assert_array_equal(cnt2, cnt_ref)
-    np.testing.assert_array_equal(med, _scipy(u, v, val, ue, ve, "median"))   # order statistics: bit-exact
-    if err is not None:
-        w = 1.0 / err ** 2
-        s_wpp = _scipy(u, v, w * val * val, ue, ve, "sum")
-        s_wp = _scipy(u, v, w * val, ue, ve, "sum")
-        s_w = _scipy(u, v, w, ue, ve, "sum")
-        with np.errstate(invalid="ignore", divide="ignore"):
-            a_ref = s_wp / s_w
-            r_ref = np.sqrt((1.0 / s_w) * (s_wpp - 2.0 * a_ref * s_wp + a_ref * a_ref * s_w))
-        a, r, sw = ops.binned_stat_2d(u, v, val, ue, ve, "weighted", err=err)
-        np.testing.assert_allclose(sw, s_w, rtol=1e-13)
-        np.testing.assert_allclose(a, a_ref, rtol=1e-12, equal_nan=True)
-        ok = np.isfinite(r_ref) & (r_ref > 1e-3 * np.nanmax(r_ref))
-        np.testing.assert_allclose(r[ok], r_ref[ok], rtol=1e-9)
+from _pair_stat_refs import _check  # noqa: E402  (the scipy comparison lives beside the other pair-statistic references)
 
 
 def test_binned_stat_random_field():

@@ -32,9 +32,13 @@ __global__ __launch_bounds__(256) void knn_mean_kernel(const double *__restrict_
             double d = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
             if (d < bd[K - 1]) {                     // strict: earlier table rows win ties
                 double v = sv[t];
+                bool ins = false;
 #pragma unroll
                 for (int j = 0; j < K; ++j) {        // insertion into the sorted list
-                    if (d < bd[j]) {
+                    // behind the slot the new row takes, every entry moves down one place, also past an equal distance:
+                    // the entry carried along came from an earlier slot, i.e. an earlier table row of the same distance
+                    ins = ins || (d < bd[j]);
+                    if (ins) {
                         const double td = bd[j], tv = bv[j];
                         bd[j] = d; bv[j] = v;
                         d = td; v = tv;
