@@ -356,6 +356,50 @@ int tgp_gp_predict_var_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k,
 int tgp_gp_loglik_grad_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
                            const double *alpha, double *grad /* nterms x 4 */);
 
+/* ---- S2i: the batched routes (S2e, S2f / S2h, S2g, S3f) for sums of kernels ---------------------------------------------------
+ * The reference's regime is many small GPs, and its most physical kernel is a sum (an atmospheric term plus a long-range optical
+ * one): one tgp_kernel_sum per problem, ks [nb], 1 .. TGP_SUM_MAX terms each, term counts and kinds differing freely between the
+ * problems of a batch.  Nothing below the K values knows what kernel built K, so factorisation, sweeps, substitution and
+ * products are the launches of the namesakes; three device parts are the sums' own:
+ *   K build      one 128 x 128 tile per workgroup as in S2e, every term evaluated in registers, the tile stored once;
+ *   posterior    the cross panels H_b (and Kss_b) the same way; the prior variance is tgp_ksum_amp(k_b);
+ *   gradient     K_b^-1 is formed once per problem; the pair pass of S2h runs once per term, over the problems whose term t has
+ *                the launch's evaluator, into partial sums of their own; the fixed-order reduction runs per (problem, term).
+ * Rounding, as in S1s / S2s: a strict-lower element of K_b (an element of H_b, an off-diagonal one of Kss_b) is
+ * ((v_0 + v_1) + v_2) + v_3, plain fp64 adds in term order, v_t bit for bit what the one-term batched build writes for term t
+ * (the amplitude multiply is rounded before the add); the diagonal of K_b is tgp_ksum_amp(k_b) + yerr_i^2, that of Kss_b exactly
+ * tgp_ksum_amp(k_b); padding rows and columns are the single-kernel build's.
+ * Launch lists: the problems of a chunk are grouped by what their own kernel needs -- one term: the evaluator's launch of the
+ * namesake; two or more Gaussian terms: an instantiation that carries no Bessel evaluator; a sum with a von Karman term: one that
+ * does.  A problem's list is decided by its kernel alone.
+ * Each entry has its namesake's arguments, limits, return codes, timings and chunking with const tgp_kernel_sum *ks in place of
+ * const tgp_kernel *ks.  tgp_gp_solve_grad_batch_sum is tgp_gp_solve_grad_batch_any with grad (nb, TGP_SUM_MAX, 4): row t of
+ * problem b is d log L / d (log amp_t, a_t, b_t, c_t) in the convention of S2h, rows t >= nterms_b are exactly 0.
+ * tgp_kbuild_batch_sum is the building block: it stages the batch, runs the batched K build at the batch's common Np and returns
+ * every problem's lower triangle with its diagonal, row-major in its nmax x nmax slot of K (nb, nmax, nmax); everything above
+ * the diagonal or beyond ns[b] is exactly 0.  No factorisation runs.  It is to the batch what tgp_d_kbuild_lower +
+ * tgp_d_unpack_lower are to the single solve; yerr may be NULL; timings [0] K build, every other slot 0.
+ * Argument errors: nterms outside 1 .. TGP_SUM_MAX or an unknown kind in any term of any problem returns -1 with a message
+ * naming the entry, the problem and the term, before anything runs on the device; the others are those of S2e.
+ * Promises: with nterms == 1 everywhere every entry IS its namesake, the same launches and the same bits.  A problem's bits
+ * depend neither on its companions, whatever their term counts and kinds, nor on its place, nor on the chunking
+ * (TGP_BATCH_CHUNK), nor on nmax wherever the namesake promises that.  A problem with info[b] > 0 leaves the others untouched,
+ * bit for bit.                                                                                                              */
+int tgp_gp_solve_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax, const double *X,
+                           const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info);
+int tgp_gp_posterior_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax,
+                               const double *X, const double *y, const double *yerr,
+                               const int64_t *ms, int64_t mmax, const double *Xs, int what,
+                               double *alpha, double *unc, double *logdet, double *ydota, int32_t *info);
+int tgp_gp_loo_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax,
+                         const double *X, const double *y, const double *yerr,
+                         double *alpha, double *invdiag, double *logdet, double *ydota, int32_t *info);
+int tgp_gp_solve_grad_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax,
+                                const double *X, const double *y, const double *yerr,
+                                double *logdet, double *ydota, double *grad /* (nb, TGP_SUM_MAX, 4) */, int32_t *info);
+int tgp_kbuild_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax,
+                         const double *X, const double *yerr, double *K);
+
 /* ---- S4: binned scalar pair correlation, exact binning -----------------------------------
  * w == NULL: unit weights.  TwoD: nbins x nbins pixels over [-max_sep, max_sep]^2, outputs
  * of length nbins^2 (flat index iy*nbins+ix).  Log: nbins log-spaced bins in

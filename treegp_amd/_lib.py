@@ -103,6 +103,13 @@ SIGNATURES = {
     "tgp_gp_predict_cov_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
     "tgp_gp_predict_var_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
     "tgp_gp_loglik_grad_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp]),
+    # seam S2i: the batched entries for sums, each its namesake's prototype with an array of tgp_kernel_sum
+    "tgp_gp_solve_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tgp_gp_posterior_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.c_int,
+                                             _vp, _vp, _vp, _vp, _vp]),
+    "tgp_gp_loo_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tgp_gp_solve_grad_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tgp_kbuild_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp]),
     "tgp_d_unpack_lower":(C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "tgp_factor_device": (C.c_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64)]),
     "tgp_debug_syrk_loop": (C.c_int, [_vp, _vp, _i64, C.c_int, _dp, _dp]),

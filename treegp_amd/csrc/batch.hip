@@ -5,7 +5,8 @@
 // panels at b * tgp_panel_elems(Np), its inverted diagonal blocks at b * Np * 128; rows >= n_b carry the identity.  Every
 // launch covers all problems of the chunk, the problem index being the grid's y dimension, and runs the existing device
 // bodies through thin wrappers that only offset pointers by it:
-//   K build        kbuild_tile (kbuild_tile.h), once per kernel evaluator present
+//   K build        kbuild_tile (kbuild_tile.h), once per kernel evaluator present; problems whose kernel is a sum of two or more
+//                  terms (seam S2i) through kbuild_tile_sum (ksum_eval.h), once per launch list present
 //   posterior, gradient   the bodies of post_tile.h, which the single-problem kernels of cov.hip call too
 //   per panel k    potrf128_body (0,0) -> rows below: X = A W0^T -> A[:,128:] -= X L10^T -> potrf128_body (1,1) ->
 //                  rows below: X = A W1^T (gemm_tile_128) -> trailing update, depth 256 (gemm_tile_dtv)
@@ -18,6 +19,7 @@
 #include "tgp_internal.h"
 #include "kernel_eval.h"
 #include "kbuild_tile.h"
+#include "ksum_eval.h"
 #include "gemm_tile.h"
 #include "post_tile.h"
 #include "potrf128.h"
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void bpad_kernel(const double *__restrict__ rX
     const int64_t s = (int64_t)b * nmax + i, d = (int64_t)b * Np + i;
     X[2 * d] = in ? rX[2 * s] : 0.0;
     X[2 * d + 1] = in ? rX[2 * s + 1] : 0.0;
-    y[d] = in ? ry[s] : 0.0;
+    if (ry) y[d] = in ? ry[s] : 0.0;                            // (the K build alone stages no values)
     if (e) e[d] = in ? re[s] : 0.0;
 }
 
@@ -54,9 +56,11 @@ __global__ __launch_bounds__(256) void bunpad_kernel(const double *__restrict__ 
     out[(int64_t)b * nmax + i] = i < ns[b] ? a[(int64_t)b * Np + i] : 0.0;
 }
 
-// ---- K + diag(yerr^2): one 128 x 128 tile per workgroup, blockIdx.y = the y-th problem of this evaluator ---------------------
+// ---- K + diag(yerr^2): one 128 x 128 tile per workgroup, blockIdx.y = the y-th problem of this launch list ---------------------
+// Every problem's kernel is a KSumParams (ksum_eval.h); a one-term problem is its term 0 and goes through the evaluator's own
+// launch, the problems of two or more terms through bkbuild_sum_kernel below.
 template <int KE>
-__global__ __launch_bounds__(256) void bkbuild_kernel(const KParams *__restrict__ kp, const int *__restrict__ list,
+__global__ __launch_bounds__(256) void bkbuild_kernel(const KSumParams *__restrict__ ksp, const int *__restrict__ list,
                                                       const int64_t *__restrict__ ns, const double *__restrict__ X,
                                                       const double *__restrict__ e, BatchDims d, double *__restrict__ A) {
     const int b = list[blockIdx.y];
@@ -64,8 +68,37 @@ __global__ __launch_bounds__(256) void bkbuild_kernel(const KParams *__restrict_
     tri_index(blockIdx.x, ti, tj);
     const int64_t pj = tj >> 1;
     double *tile = A + b * d.ae + panel_off(pj, d.Np) + (ti * TGP_TB - pj * TGP_PW) * TGP_PW + (tj & 1) * TGP_TB;
-    const KParams p = kp[b];
+    const KParams p = ksp[b].t[0];
     kbuild_tile<KE>(p, X + (int64_t)b * 2 * d.Np, ns[b], e ? e + (int64_t)b * d.Np : nullptr, ti, tj, tile);
+}
+
+// The same tile for the problems of 2 .. TGP_SUM_MAX terms (seam S2i): every term in registers, the tile stored once
+// (kbuild_tile_sum).  Two launch lists and two instantiations: ANYVK = false takes the sums of Gaussian terms only and carries no
+// Bessel evaluator, ANYVK = true the sums with a von Karman term.  A problem's list follows from its own kernel alone.
+template <bool ANYVK>
+__global__ __launch_bounds__(256) void bkbuild_sum_kernel(const KSumParams *__restrict__ ksp, const int *__restrict__ list,
+                                                          const int64_t *__restrict__ ns, const double *__restrict__ X,
+                                                          const double *__restrict__ e, BatchDims d, double *__restrict__ A) {
+    const int b = list[blockIdx.y];
+    int64_t ti, tj;
+    tri_index(blockIdx.x, ti, tj);
+    const int64_t pj = tj >> 1;
+    double *tile = A + b * d.ae + panel_off(pj, d.Np) + (ti * TGP_TB - pj * TGP_PW) * TGP_PW + (tj & 1) * TGP_TB;
+    kbuild_tile_sum<ANYVK>(ksp[b], X + (int64_t)b * 2 * d.Np, ns[b], e ? e + (int64_t)b * d.Np : nullptr, ti, tj, tile);
+}
+
+// problem b's lower triangle with its diagonal from the packed panels to the caller's row-major (nmax x nmax) slot, exactly 0
+// above the diagonal and beyond n_b; blockIdx.x = 256-column group + groups * row
+__global__ __launch_bounds__(256) void bunpack_lower_kernel(const double *__restrict__ A, const int64_t *__restrict__ ns, BatchDims d,
+                                                            int64_t nmax, double *__restrict__ out) {
+    const int b = blockIdx.y;
+    const int64_t ng = (nmax + 255) / 256;
+    const int64_t i = blockIdx.x / ng;
+    const int64_t j = (blockIdx.x % ng) * 256 + threadIdx.x;
+    if (j >= nmax) return;
+    const int64_t pj = j >> 8;
+    out[((int64_t)b * nmax + i) * nmax + j] =
+        (i < ns[b] && j <= i) ? A[b * d.ae + panel_off(pj, d.Np) + (i - pj * TGP_PW) * TGP_PW + (j & 255)] : 0.0;
 }
 
 // ---- factorisation ----------------------------------------------------------------------------------------------------------
@@ -218,7 +251,7 @@ struct PostDims {
 // Every element of the Mp x ncols panels is written.  blockIdx.x = 256-column group + (ncols / 256) * row, blockIdx.y = the
 // y-th problem of this evaluator.  Xs: the caller's (nb, mmax, 2) rows, read below m_b only; X: the staged (nb, Np, 2).
 template <int KE>
-__global__ __launch_bounds__(256) void bcross_kernel(const KParams *__restrict__ kp, const int *__restrict__ list,
+__global__ __launch_bounds__(256) void bcross_kernel(const KSumParams *__restrict__ ksp, const int *__restrict__ list,
                                                      const int64_t *__restrict__ ns, const int64_t *__restrict__ ms,
                                                      const double *__restrict__ Xs, const double *__restrict__ X, int64_t Np,
                                                      PostDims q, int self, int64_t ncols, double *__restrict__ out) {
@@ -229,8 +262,25 @@ __global__ __launch_bounds__(256) void bcross_kernel(const KParams *__restrict__
     const int64_t m = ms[b], n = self ? m : ns[b];
     const double *xs = Xs + (int64_t)b * 2 * q.mmax;
     const double *x = self ? xs : X + (int64_t)b * 2 * Np;
-    const KParams p = kp[b];
+    const KParams p = ksp[b].t[0];
     out[(int64_t)b * q.Mp * ncols + panel_elem(i, j, q.Mp)] = cross_value<KE>(p, xs, m, x, n, self, i, j);
+}
+
+// the same for the problems of 2 .. TGP_SUM_MAX terms: cross_value<KE> per term, added in term order (cross_value_sum); on
+// `self` the diagonal is exactly the sum of the amplitudes.  Launch lists and instantiations as bkbuild_sum_kernel.
+template <bool ANYVK>
+__global__ __launch_bounds__(256) void bcross_sum_kernel(const KSumParams *__restrict__ ksp, const int *__restrict__ list,
+                                                         const int64_t *__restrict__ ns, const int64_t *__restrict__ ms,
+                                                         const double *__restrict__ Xs, const double *__restrict__ X, int64_t Np,
+                                                         PostDims q, int self, int64_t ncols, double *__restrict__ out) {
+    const int b = list[blockIdx.y];
+    const int64_t ng = ncols / 256;
+    const int64_t i = blockIdx.x / ng;
+    const int64_t j = (blockIdx.x % ng) * 256 + threadIdx.x;
+    const int64_t m = ms[b], n = self ? m : ns[b];
+    const double *xs = Xs + (int64_t)b * 2 * q.mmax;
+    const double *x = self ? xs : X + (int64_t)b * 2 * Np;
+    out[(int64_t)b * q.Mp * ncols + panel_elem(i, j, q.Mp)] = cross_value_sum<ANYVK>(ksp[b], xs, m, x, n, self, i, j);
 }
 
 // Bt_b[:, kb] <- Bt_b[:, kb] W_kb^T, one 128-row tile per workgroup
@@ -253,8 +303,9 @@ __global__ __launch_bounds__(256, 2) void bupdate_kernel(double *Bt, const doubl
     post_update_tile(Bt + (int64_t)b * q.Mp * d.Np, q.Mp, A + b * d.ae, d.Np, kb, 0, ti, c);
 }
 
-// var_b[i] = amp_b - |Bt_b[i, :]|^2 over all Np / 256 panels, one wave per row (row_sqnorm_wave); rows >= m_b are 0
-__global__ __launch_bounds__(256) void bvar_rows_kernel(const double *__restrict__ Bt, const KParams *__restrict__ kp,
+// var_b[i] = amp_b - |Bt_b[i, :]|^2 over all Np / 256 panels, one wave per row (row_sqnorm_wave); rows >= m_b are 0.  amp_b: the
+// prior variance, the amplitudes of problem b's terms added in term order
+__global__ __launch_bounds__(256) void bvar_rows_kernel(const double *__restrict__ Bt, const KSumParams *__restrict__ ksp,
                                                         const int64_t *__restrict__ ms, int64_t Np, PostDims q,
                                                         double *__restrict__ var) {
     const int b = blockIdx.y;
@@ -267,7 +318,7 @@ __global__ __launch_bounds__(256) void bvar_rows_kernel(const double *__restrict
         return;
     }
     const double acc = row_sqnorm_wave(Bt + (int64_t)b * q.Mp * Np, q.Mp, (int)(Np / TGP_PW), i);
-    if (lane == 0) *out = kp[b].amp - acc;
+    if (lane == 0) *out = ksp[b].ampsum - acc;
 }
 
 // C_b(ti, tj) -= sum over all panels of Bt_b[ti] Bt_b[tj]^T; blockIdx.x = ti + mt * tj
@@ -336,32 +387,36 @@ __global__ __launch_bounds__(256, 2) void bkinv_syrk_kernel(double *C, const dou
     post_syrk_tile(C + (int64_t)b * Np * Np, Bt + (int64_t)b * Np * Np, Np, nP, ti, tj, ti >> 1);
 }
 
-// loglik_grad_block<KE> for problem b = list[blockIdx.y] (the chunk's problems of evaluator KE, as the K build takes them): 64 rows
-// (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the lower triangle below n_b, four partial sums per workgroup at
-// partial[(b * nrb * nP + blockIdx.x) * 4].  One launch per evaluator present and not one kernel that branches on kp[b].kind:
+// loglik_grad_block<KE> for term `term` of problem b = list[blockIdx.y] (the chunk's problems whose term `term` has evaluator KE):
+// 64 rows (blockIdx.x / nP) x one 256-column panel (blockIdx.x % nP) of the lower triangle below n_b, four partial sums per
+// workgroup at partial[((b * T + term) * nrb * nP + blockIdx.x) * 4], T the rows of the result per problem (1, or TGP_SUM_MAX).  One launch per evaluator present and not one kernel that branches on kp[b].kind:
 // the three bodies in one kernel take the von Karman bodies' 166 VGPRs (3 waves per SIMD) for the Gaussian problems too, whose
 // own body needs 60 (8 waves per SIMD).  A problem's workgroups and sums are the same whichever launch its companions are in.
 template <int KE>
-__global__ __launch_bounds__(256) void bloglik_grad_kernel(const KParams *__restrict__ kp, const int *__restrict__ list,
-                                                           const int64_t *__restrict__ ns, const double *__restrict__ X,
+__global__ __launch_bounds__(256) void bloglik_grad_kernel(const KSumParams *__restrict__ ksp, const int *__restrict__ list, int term,
+                                                           int T, const int64_t *__restrict__ ns, const double *__restrict__ X,
                                                            const double *__restrict__ alpha, const double *__restrict__ C, int64_t Np,
                                                            GradDims g, double *__restrict__ partial) {
     const int b = list[blockIdx.y];
     const int64_t n = ns[b];
     const int64_t pj = blockIdx.x % g.nP, i0 = (int64_t)(blockIdx.x / g.nP) * 64;
     if (i0 >= n || pj * TGP_PW >= n) return;                      // whole workgroups leave together; never summed
-    const KParams p = kp[b];
+    const KParams p = ksp[b].t[term];
     loglik_grad_block<KE>(p, X + (int64_t)b * 2 * Np, alpha + (int64_t)b * Np, C + (int64_t)b * Np * Np, Np, n, pj, i0,
-                          partial + (((int64_t)b * g.nrb * g.nP) + blockIdx.x) * 4);
+                          partial + ((((int64_t)b * T + term) * g.nrb * g.nP) + blockIdx.x) * 4);
 }
 
-// one workgroup per problem: its partial sums (row blocks below n_b x panels below n_b, that order) in a fixed order that depends
-// on n_b alone
-__global__ __launch_bounds__(256) void bloglik_grad_reduce_kernel(const double *__restrict__ partial, const int64_t *__restrict__ ns,
-                                                                  GradDims g, double *__restrict__ out) {
-    const int b = blockIdx.x;
+// one workgroup per problem (blockIdx.x) and term (blockIdx.y): its partial sums (row blocks below n_b x panels below n_b, that
+// order) in a fixed order that depends on n_b alone.  Rows at or beyond the problem's term count are left as they are (zeroed
+// by the host before the launch).
+__global__ __launch_bounds__(256) void bloglik_grad_reduce_kernel(const double *__restrict__ partial, const KSumParams *__restrict__ ksp,
+                                                                  int T, const int64_t *__restrict__ ns, GradDims g,
+                                                                  double *__restrict__ out) {
+    const int b = blockIdx.x, t = blockIdx.y;
+    if (t >= ksp[b].nterms) return;
     const int64_t n = ns[b];
-    loglik_grad_reduce(partial + (int64_t)b * g.nrb * g.nP * 4, (n + 63) / 64, (n + TGP_PW - 1) / TGP_PW, g.nP, out + (int64_t)b * 4);
+    loglik_grad_reduce(partial + ((int64_t)b * T + t) * g.nrb * g.nP * 4, (n + 63) / 64, (n + TGP_PW - 1) / TGP_PW, g.nP,
+                       out + ((int64_t)b * T + t) * 4);
 }
 
 // ---- diag(K^-1) of every problem (seam S2g): the substitution of S2f without its C_b ---------------------------------------------
@@ -430,8 +485,18 @@ static int64_t batch_chunk(tgp_ctx *ctx, const char *fn, int nb, size_t per, siz
     return c;
 }
 
-// nb, nmax, ns[b] and the kinds, as both batched entries take them; -1 with a message naming `fn`
-static int batch_check(tgp_ctx *ctx, const char *fn, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax) {
+// The kernels of a batch: the one kernel per problem of the entries of S2e .. S3f, or the sums of seam S2i.  The core below takes
+// sums; an old entry's problems are sums of one term.
+struct KSrc {
+    const tgp_kernel *k1;
+    const tgp_kernel_sum *ks;
+    int nterms(int64_t b) const { return ks ? ks[b].nterms : 1; }
+    const tgp_kernel *term(int64_t b, int t) const { return ks ? &ks[b].term[t] : &k1[b]; }
+};
+
+// nb, nmax, ns[b] and the kinds (of a sum: the term count and every term's kind), as every batched entry takes them; -1 with a
+// message naming `fn`, the problem and the term
+static int batch_check(tgp_ctx *ctx, const char *fn, int nb, const KSrc &ks, const int64_t *ns, int64_t nmax) {
     const std::string f(fn);
     if (nb < 1) { ctx->err = f + ": nb must be >= 1"; return -1; }
     if (nmax < 1 || nmax > 4096) { ctx->err = f + ": nmax must be in 1 .. 4096 (larger problems: tgp_gp_solve)"; return -1; }
@@ -441,30 +506,49 @@ static int batch_check(tgp_ctx *ctx, const char *fn, int nb, const tgp_kernel *k
                        std::to_string((long long)nmax);
             return -1;
         }
-        if (kind_to_ke(ks[b].kind) < 0) {
-            ctx->err = f + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks[b].kind) + " is not a kernel kind";
+        if (!ks.ks) {
+            if (kind_to_ke(ks.k1[b].kind) < 0) {
+                ctx->err = f + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks.k1[b].kind) + " is not a kernel kind";
+                return -1;
+            }
+            continue;
+        }
+        const int nt = ks.ks[b].nterms;
+        if (nt < 1 || nt > TGP_SUM_MAX) {
+            ctx->err = f + ": ks[" + std::to_string(b) + "].nterms = " + std::to_string(nt) + " is outside 1 .. " +
+                       std::to_string(TGP_SUM_MAX);
             return -1;
         }
+        for (int t = 0; t < nt; ++t)
+            if (kind_to_ke(ks.ks[b].term[t].kind) < 0) {
+                ctx->err = f + ": ks[" + std::to_string(b) + "].term[" + std::to_string(t) + "].kind = " +
+                           std::to_string(ks.ks[b].term[t].kind) + " is not a kernel kind";
+                return -1;
+            }
     }
     return 0;
 }
 
+// launch lists of the kernels that evaluate kernel values (K build, cross panels): the one-term problems by evaluator, then the
+// sums of Gaussian terms only, then the sums with a von Karman term
+enum { BL_GAUSS = 0, BL_VK = 1, BL_AVK = 2, BL_SUM_GAUSS = 3, BL_SUM_VK = 4, BL_N = 5 };
+
 // the per-problem arrays of one chunk of S2e (device arena + pinned host tables); the posterior's own arrays follow them
 struct BatchBufs {
     double *dA, *dW, *dX, *dy, *de, *dz, *da, *rX, *ry, *re, *ra, *dout;
-    KParams *dkp;
+    KSumParams *dks;
     int64_t *dns;
-    int *dlist, *dinfo;
-    KParams *hkp;
+    int *dlist, *dglist, *dinfo;
+    KSumParams *hks;
     int64_t *hns;
-    int *hlist, *hinfo;
+    int *hlist, *hglist, *hinfo;
     double *hout;
-    int cnt[3], start[3];          // the chunk's evaluator lists: problems per evaluator and where each starts in dlist
+    int cnt[BL_N], start[BL_N];    // the chunk's launch lists: problems per list and where each starts in dlist
 };
 
 static size_t batch_bytes_per_problem(const BatchDims &d, int64_t nmax) {
     return rup((size_t)d.ae * 8) + rup((size_t)d.we * 8) + 6 * rup((size_t)d.Np * 8) + 5 * rup((size_t)nmax * 8) +
-           rup(sizeof(KParams)) + 2 * rup(8) + 2 * rup(16);
+           rup(sizeof(KSumParams)) + 2 * rup(8) + 3 * rup(16);
 }
 
 // carves C problems' arrays of S2e out of the arena at `base` (+ *off) and the pinned host scratch
@@ -482,21 +566,24 @@ static int batch_take(tgp_ctx *ctx, const BatchDims &d, int64_t nmax, int64_t C,
     bb->ry = (double *)take((size_t)C * nmax * 8);
     bb->re = (double *)take((size_t)C * nmax * 8);
     bb->ra = (double *)take((size_t)C * nmax * 8);
-    bb->dkp = (KParams *)take((size_t)C * sizeof(KParams));
+    bb->dks = (KSumParams *)take((size_t)C * sizeof(KSumParams));
     bb->dns = (int64_t *)take((size_t)C * 8);
     bb->dlist = (int *)take((size_t)C * 4);
+    bb->dglist = (int *)take((size_t)C * 4 * TGP_SUM_MAX);     // the gradient's lists: one set per term (solve_grad_batch)
     bb->dinfo = (int *)take((size_t)C * 4);
     bb->dout = (double *)take((size_t)C * 16);
     // host side of the small tables and results: the context's pinned scratch
-    const size_t hbytes = rup((size_t)C * sizeof(KParams)) + rup((size_t)C * 8) + rup((size_t)C * 4) + rup((size_t)C * 4) + rup((size_t)C * 16);
+    const size_t hbytes = rup((size_t)C * sizeof(KSumParams)) + rup((size_t)C * 8) + rup((size_t)C * 4) +
+                          rup((size_t)C * 4 * TGP_SUM_MAX) + rup((size_t)C * 4) + rup((size_t)C * 16);
     void *hp = nullptr;
     int rc = tgp_ensure_pinned(ctx, hbytes, &hp);
     if (rc) return rc;
     char *hb = (char *)hp;
-    bb->hkp = (KParams *)hb;
-    bb->hns = (int64_t *)(hb + rup((size_t)C * sizeof(KParams)));
+    bb->hks = (KSumParams *)hb;
+    bb->hns = (int64_t *)(hb + rup((size_t)C * sizeof(KSumParams)));
     bb->hlist = (int *)((char *)bb->hns + rup((size_t)C * 8));
-    bb->hinfo = (int *)((char *)bb->hlist + rup((size_t)C * 4));
+    bb->hglist = (int *)((char *)bb->hlist + rup((size_t)C * 4));
+    bb->hinfo = (int *)((char *)bb->hglist + rup((size_t)C * 4 * TGP_SUM_MAX));
     bb->hout = (double *)((char *)bb->hinfo + rup((size_t)C * 4));
     static bool attr_ok = hipFuncSetAttribute((const void *)bpotrf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                               (int)potrf_v2::POTRF_LDS_BYTES) == hipSuccess;
@@ -504,48 +591,73 @@ static int batch_take(tgp_ctx *ctx, const BatchDims &d, int64_t nmax, int64_t C,
     return 0;
 }
 
-// problems c0 .. c0 + cn of the batch: staging, K build, factorisation, sweeps and logdet / chi2, on the context's stream; alpha
-// (padded, Np) in bb.da and unpadded in bb.ra when `want_alpha`.  Events: ev[0] .. ev[1] K build, .. ev[2] Cholesky, .. ev[3]
-// sweeps.  Nothing is copied back and the stream is not synchronised.
-static int batch_factor_chunk(tgp_ctx *ctx, const BatchDims &d, BatchBufs &bb, int64_t c0, int64_t cn, const tgp_kernel *ks,
-                              const int64_t *ns, int64_t nmax, const double *X, const double *y, const double *yerr, bool want_alpha) {
+// the launch list of problem b's kernel: decided by that kernel alone
+static int batch_list_of(const KSumParams &k) {
+    if (k.nterms == 1) return k.ke[0];                            // (BL_GAUSS .. BL_AVK are the evaluators' own numbers)
+    return k.any_vk ? BL_SUM_VK : BL_SUM_GAUSS;
+}
+
+// problems c0 .. c0 + cn of the batch: the small tables and the caller's rows to the device, the rows padded to Np, then
+// K + diag(yerr^2) of every problem into its packed panels (ev[0] .. ev[1]), one launch per launch list present.  y may be NULL.
+static int batch_build_chunk(tgp_ctx *ctx, const BatchDims &d, BatchBufs &bb, int64_t c0, int64_t cn, const KSrc &ks,
+                             const int64_t *ns, int64_t nmax, const double *X, const double *y, const double *yerr) {
     hipStream_t st = ctx->stream;
-    const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
-    // evaluator lists: the problems of this chunk grouped by kernel evaluator, each group in batch order
+    const int64_t Np = d.Np, nT = Np / TGP_TB;
+    // launch lists: the problems of this chunk grouped by what their kernel needs, each group in batch order
     int *cnt = bb.cnt, *start = bb.start;
-    cnt[0] = cnt[1] = cnt[2] = 0;
+    for (int l = 0; l < BL_N; ++l) cnt[l] = 0;
     for (int64_t b = 0; b < cn; ++b) {
-        bb.hkp[b] = make_kparams(&ks[c0 + b]);
-        bb.hns[b] = ns[c0 + b];
-        ++cnt[kind_to_ke(ks[c0 + b].kind)];
+        const int64_t gb = c0 + b;
+        bb.hks[b] = make_ksum_terms(ks.nterms(gb), [&](int t) { return ks.term(gb, t); }, false);
+        bb.hns[b] = ns[gb];
+        ++cnt[batch_list_of(bb.hks[b])];
     }
     start[0] = 0;
-    start[1] = cnt[0];
-    start[2] = cnt[0] + cnt[1];
-    int fill[3] = {0, 0, 0};
+    for (int l = 1; l < BL_N; ++l) start[l] = start[l - 1] + cnt[l - 1];
+    int fill[BL_N] = {0, 0, 0, 0, 0};
     for (int64_t b = 0; b < cn; ++b) {
-        const int k = kind_to_ke(ks[c0 + b].kind);
-        bb.hlist[start[k] + fill[k]++] = (int)b;
+        const int l = batch_list_of(bb.hks[b]);
+        bb.hlist[start[l] + fill[l]++] = (int)b;
     }
-    TGP_HIP(hipMemcpyAsync(bb.dkp, bb.hkp, (size_t)cn * sizeof(KParams), hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(bb.dks, bb.hks, (size_t)cn * sizeof(KSumParams), hipMemcpyHostToDevice, st));
     TGP_HIP(hipMemcpyAsync(bb.dns, bb.hns, (size_t)cn * 8, hipMemcpyHostToDevice, st));
     TGP_HIP(hipMemcpyAsync(bb.dlist, bb.hlist, (size_t)cn * 4, hipMemcpyHostToDevice, st));
     TGP_HIP(hipMemcpyAsync(bb.rX, X + c0 * nmax * 2, (size_t)cn * nmax * 16, hipMemcpyHostToDevice, st));
-    TGP_HIP(hipMemcpyAsync(bb.ry, y + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
+    if (y) TGP_HIP(hipMemcpyAsync(bb.ry, y + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
     if (yerr) TGP_HIP(hipMemcpyAsync(bb.re, yerr + c0 * nmax, (size_t)cn * nmax * 8, hipMemcpyHostToDevice, st));
     TGP_HIP(hipMemsetAsync(bb.dinfo, 0, (size_t)cn * 4, st));
     const unsigned ncn = (unsigned)cn;
-    double *dA = bb.dA, *dW = bb.dW;
-    bpad_kernel<<<dim3((unsigned)(Np / 256), ncn), 256, 0, st>>>(bb.rX, bb.ry, yerr ? bb.re : nullptr, bb.dns, nmax, Np, bb.dX, bb.dy,
-                                                                 yerr ? bb.de : nullptr);
+    double *dA = bb.dA;
+    bpad_kernel<<<dim3((unsigned)(Np / 256), ncn), 256, 0, st>>>(bb.rX, y ? bb.ry : nullptr, yerr ? bb.re : nullptr, bb.dns, nmax, Np,
+                                                                 bb.dX, bb.dy, yerr ? bb.de : nullptr);
     const double *e_or_null = yerr ? bb.de : nullptr;
 
     TGP_HIP(hipEventRecord(ctx->ev[0], st));
     const unsigned ntiles = (unsigned)(nT * (nT + 1) / 2);
-    if (cnt[0]) bkbuild_kernel<KE_GAUSS><<<dim3(ntiles, cnt[0]), 256, 0, st>>>(bb.dkp, bb.dlist + start[0], bb.dns, bb.dX, e_or_null, d, dA);
-    if (cnt[1]) bkbuild_kernel<KE_VK><<<dim3(ntiles, cnt[1]), 256, 0, st>>>(bb.dkp, bb.dlist + start[1], bb.dns, bb.dX, e_or_null, d, dA);
-    if (cnt[2]) bkbuild_kernel<KE_AVK><<<dim3(ntiles, cnt[2]), 256, 0, st>>>(bb.dkp, bb.dlist + start[2], bb.dns, bb.dX, e_or_null, d, dA);
+#define TGP_BUILD(KERNEL, l)                                                                                                      \
+    if (cnt[l]) KERNEL<<<dim3(ntiles, cnt[l]), 256, 0, st>>>(bb.dks, bb.dlist + start[l], bb.dns, bb.dX, e_or_null, d, dA);
+    TGP_BUILD(bkbuild_kernel<KE_GAUSS>, BL_GAUSS)
+    TGP_BUILD(bkbuild_kernel<KE_VK>, BL_VK)
+    TGP_BUILD(bkbuild_kernel<KE_AVK>, BL_AVK)
+    TGP_BUILD(bkbuild_sum_kernel<false>, BL_SUM_GAUSS)
+    TGP_BUILD(bkbuild_sum_kernel<true>, BL_SUM_VK)
+#undef TGP_BUILD
     TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    TGP_HIP(hipGetLastError());
+    return 0;
+}
+
+// problems c0 .. c0 + cn of the batch: staging and K build (batch_build_chunk), factorisation, sweeps and logdet / chi2, on the
+// context's stream; alpha (padded, Np) in bb.da and unpadded in bb.ra when `want_alpha`.  Events: ev[0] .. ev[1] K build, .. ev[2]
+// Cholesky, .. ev[3] sweeps.  Nothing is copied back and the stream is not synchronised.
+static int batch_factor_chunk(tgp_ctx *ctx, const BatchDims &d, BatchBufs &bb, int64_t c0, int64_t cn, const KSrc &ks,
+                              const int64_t *ns, int64_t nmax, const double *X, const double *y, const double *yerr, bool want_alpha) {
+    int rc = batch_build_chunk(ctx, d, bb, c0, cn, ks, ns, nmax, X, y, yerr);
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
+    const unsigned ncn = (unsigned)cn;
+    double *dA = bb.dA, *dW = bb.dW;
 
     // right-looking, one 256-wide panel at a time
     for (int k = 0; k < (int)nP; ++k) {
@@ -612,7 +724,7 @@ struct BatchRun {
 };
 
 // after the caller's own NULL checks: nb, nmax, ns and the kinds (batch_check), then the geometry.  Touches no device.
-static int batch_begin(BatchRun &r, tgp_ctx *ctx, const char *fn, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+static int batch_begin(BatchRun &r, tgp_ctx *ctx, const char *fn, int nb, const KSrc &ks, const int64_t *ns, int64_t nmax,
                        double *alpha, double *logdet, double *ydota, int32_t *info) {
     int rc = batch_check(ctx, fn, nb, ks, ns, nmax);
     if (rc) return rc;
@@ -667,12 +779,12 @@ static void batch_finish(const BatchRun &r) {
     for (int i = 0; i < 5; ++i) r.ctx->timings[slot[i]] = r.ms[i];
 }
 
-int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+static int solve_batch(tgp_ctx *ctx, const char *fn, int nb, const KSrc &ks, const int64_t *ns, int64_t nmax, const double *X,
                        const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
     if (!ctx) return -1;
-    TGP_ARG(ks && ns && X && y && logdet && info);
+    TGP_ARG((ks.k1 || ks.ks) && ns && X && y && logdet && info);
     BatchRun r;
-    int rc = batch_begin(r, ctx, "tgp_gp_solve_batch", nb, ks, ns, nmax, alpha, logdet, ydota, info);
+    int rc = batch_begin(r, ctx, fn, nb, ks, ns, nmax, alpha, logdet, ydota, info);
     if (rc) return rc;
     rc = batch_arena(r, 0);
     if (rc) return rc;
@@ -688,6 +800,52 @@ int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t
     return 0;
 }
 
+int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                       const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
+    return solve_batch(ctx, "tgp_gp_solve_batch", nb, KSrc{ks, nullptr}, ns, nmax, X, y, yerr, alpha, logdet, ydota, info);
+}
+
+int tgp_gp_solve_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax, const double *X,
+                           const double *y, const double *yerr, double *alpha, double *logdet, double *ydota, int32_t *info) {
+    return solve_batch(ctx, "tgp_gp_solve_batch_sum", nb, KSrc{nullptr, ks}, ns, nmax, X, y, yerr, alpha, logdet, ydota, info);
+}
+
+// ---- S2i: the batched K build alone, every problem's lower triangle back on the host (the building block of seam S2i) --------
+int tgp_kbuild_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax, const double *X,
+                         const double *yerr, double *K) {
+    static const char *fn = "tgp_kbuild_batch_sum";
+    if (!ctx) return -1;
+    if (!(ks && ns && X && K)) {
+        ctx->err = "tgp_kbuild_batch_sum: ks, ns, X and K must not be NULL";
+        return -1;
+    }
+    BatchRun r;
+    int rc = batch_begin(r, ctx, fn, nb, KSrc{nullptr, ks}, ns, nmax, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    // per problem beside S2e's arrays: the lower triangle in the caller's layout
+    rc = batch_arena(r, rup((size_t)nmax * nmax * 8));
+    if (rc) return rc;
+    hipStream_t st = ctx->stream;
+    const int64_t C = r.C;
+    double *dK = (double *)r.take((size_t)C * nmax * nmax * 8);
+    double ms = 0.0;
+    for (int64_t c0 = 0; c0 < nb; c0 += C) {
+        const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
+        rc = batch_build_chunk(ctx, r.d, r.bb, c0, cn, KSrc{nullptr, ks}, ns, nmax, X, nullptr, yerr);
+        if (rc) return rc;
+        bunpack_lower_kernel<<<dim3((unsigned)(nmax * ((nmax + 255) / 256)), (unsigned)cn), 256, 0, st>>>(r.bb.dA, r.bb.dns, r.d, nmax, dK);
+        TGP_HIP(hipGetLastError());
+        TGP_HIP(hipMemcpyAsync(K + (size_t)c0 * nmax * nmax, dK, (size_t)cn * nmax * nmax * 8, hipMemcpyDeviceToHost, st));
+        TGP_HIP(hipStreamSynchronize(st));
+        float t = 0.f;
+        TGP_HIP(hipEventElapsedTime(&t, ctx->ev[0], ctx->ev[1]));
+        ms += t;
+    }
+    for (int i = 0; i < TGP_NTIMINGS; ++i) ctx->timings[i] = 0.0;
+    ctx->timings[0] = ms;
+    return 0;
+}
+
 // ---- S3f: the posterior variance or covariance of every problem of S2e from its factor, in the same call -------------------
 // Per chunk, after batch_factor_chunk: H_b into Bt_b (and Kss_b into C_b), the block substitution Bt_b <- H_b L_b^-T over the
 // 128-column blocks kb (trsm with W_kb, update of the blocks to its right), then amp_b - |Bt_b[i, :]|^2 or Kss_b - Bt_b Bt_b^T,
@@ -695,17 +853,16 @@ int tgp_gp_solve_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t
 #define TGP_POST_VAR_MMAX TGP_VAR_CHUNK_MAX       // the variance's rows go through a row grid, as in cov.hip
 #define TGP_POST_COV_MMAX 4096
 
-int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+static int posterior_batch(tgp_ctx *ctx, const char *fn, int nb, const KSrc &ks, const int64_t *ns, int64_t nmax, const double *X,
                            const double *y, const double *yerr, const int64_t *ms, int64_t mmax, const double *Xs, int what,
                            double *alpha, double *unc, double *logdet, double *ydota, int32_t *info) {
-    static const char *fn = "tgp_gp_posterior_batch";
     if (!ctx) return -1;
-    if (!(ks && ns && X && y && ms && Xs && unc && logdet && info)) {
-        ctx->err = "tgp_gp_posterior_batch: ks, ns, X, y, ms, Xs, unc, logdet and info must not be NULL";
+    if (!((ks.k1 || ks.ks) && ns && X && y && ms && Xs && unc && logdet && info)) {
+        ctx->err = std::string(fn) + ": ks, ns, X, y, ms, Xs, unc, logdet and info must not be NULL";
         return -1;
     }
     if (what != 1 && what != 2) {
-        ctx->err = "tgp_gp_posterior_batch: what = " + std::to_string(what) + " is neither 1 (variance) nor 2 (covariance)";
+        ctx->err = std::string(fn) + ": what = " + std::to_string(what) + " is neither 1 (variance) nor 2 (covariance)";
         return -1;
     }
     BatchRun r;
@@ -749,17 +906,19 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
         TGP_HIP(hipMemcpyAsync(dms, ms + c0, (size_t)cn * 8, hipMemcpyHostToDevice, st));
         TGP_HIP(hipMemcpyAsync(dXs, Xs + c0 * mmax * 2, (size_t)cn * mmax * 16, hipMemcpyHostToDevice, st));
         TGP_HIP(hipEventRecord(ctx->ev[4], st));
-        // H_b (and Kss_b), one launch per kernel evaluator present, as the K build
+        // H_b (and Kss_b), one launch per launch list present, as the K build
         const unsigned gh = (unsigned)(q.Mp * (Np / 256)), gk = (unsigned)(q.Mp * (q.Mp / 256));
         const int *cnt = bb.cnt, *start = bb.start;
-#define TGP_CROSS(KE, i)                                                                                                          \
+#define TGP_CROSS(KERNEL, i)                                                                                                      \
         if (cnt[i]) {                                                                                                                 \
-            bcross_kernel<KE><<<dim3(gh, cnt[i]), 256, 0, st>>>(bb.dkp, bb.dlist + start[i], bb.dns, dms, dXs, bb.dX, Np, q, 0, Np, dBt); \
-            if (cov) bcross_kernel<KE><<<dim3(gk, cnt[i]), 256, 0, st>>>(bb.dkp, bb.dlist + start[i], bb.dns, dms, dXs, bb.dX, Np, q, 1, q.Mp, dC); \
+            KERNEL<<<dim3(gh, cnt[i]), 256, 0, st>>>(bb.dks, bb.dlist + start[i], bb.dns, dms, dXs, bb.dX, Np, q, 0, Np, dBt);      \
+            if (cov) KERNEL<<<dim3(gk, cnt[i]), 256, 0, st>>>(bb.dks, bb.dlist + start[i], bb.dns, dms, dXs, bb.dX, Np, q, 1, q.Mp, dC); \
         }
-        TGP_CROSS(KE_GAUSS, 0)
-        TGP_CROSS(KE_VK, 1)
-        TGP_CROSS(KE_AVK, 2)
+        TGP_CROSS(bcross_kernel<KE_GAUSS>, BL_GAUSS)
+        TGP_CROSS(bcross_kernel<KE_VK>, BL_VK)
+        TGP_CROSS(bcross_kernel<KE_AVK>, BL_AVK)
+        TGP_CROSS(bcross_sum_kernel<false>, BL_SUM_GAUSS)
+        TGP_CROSS(bcross_sum_kernel<true>, BL_SUM_VK)
 #undef TGP_CROSS
         // Bt_b <- H_b L_b^-T
         for (int kb = 0; kb < (int)nT; ++kb) {
@@ -771,7 +930,7 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
             bsyrk_cov_kernel<<<dim3((unsigned)(mt * mt), ncn), 256, 0, st>>>(dC, dBt, dms, Np, q, mt);
             bunpad_cov_kernel<<<dim3((unsigned)(mmax * ((mmax + 255) / 256)), ncn), 256, 0, st>>>(dC, dms, q, dU);
         } else {
-            bvar_rows_kernel<<<dim3((unsigned)((mmax + 3) / 4), ncn), 256, 0, st>>>(dBt, bb.dkp, dms, Np, q, dU);
+            bvar_rows_kernel<<<dim3((unsigned)((mmax + 3) / 4), ncn), 256, 0, st>>>(dBt, bb.dks, dms, Np, q, dU);
         }
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[5], st));
@@ -780,6 +939,20 @@ int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int
     }
     batch_finish(r);
     return 0;
+}
+
+int tgp_gp_posterior_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
+                           const double *y, const double *yerr, const int64_t *ms, int64_t mmax, const double *Xs, int what,
+                           double *alpha, double *unc, double *logdet, double *ydota, int32_t *info) {
+    return posterior_batch(ctx, "tgp_gp_posterior_batch", nb, KSrc{ks, nullptr}, ns, nmax, X, y, yerr, ms, mmax, Xs, what, alpha, unc,
+                           logdet, ydota, info);
+}
+
+int tgp_gp_posterior_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax, const double *X,
+                               const double *y, const double *yerr, const int64_t *ms, int64_t mmax, const double *Xs, int what,
+                               double *alpha, double *unc, double *logdet, double *ydota, int32_t *info) {
+    return posterior_batch(ctx, "tgp_gp_posterior_batch_sum", nb, KSrc{nullptr, ks}, ns, nmax, X, y, yerr, ms, mmax, Xs, what, alpha,
+                           unc, logdet, ydota, info);
 }
 
 // Bt_b <- L_b^-T for the `ncn` problems of a chunk, Bt_b holding the identity (S2f and S2g): the block substitution over the
@@ -799,12 +972,15 @@ static void batch_subst_identity(hipStream_t st, double *dBt, const BatchBufs &b
 // ---- S2f: the likelihood gradient of every problem of S2e from its factor and alpha, in the same call ---------------------------
 // Per chunk, after batch_factor_chunk with both sweeps: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row
 // tiles, C_b = -Bt_b Bt_b^T over the lower tile pairs, the reduction against dK/dp and one fixed-order sum per problem.
-// `any`: the entry of seam S2h, which takes the von Karman kinds too (one pair-sum launch per kernel class in the chunk)
-static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax,
+// `any`: the entry of seam S2h, which takes the von Karman kinds too (one pair-sum launch per kernel class in the chunk).
+// T: rows of `grad` per problem -- 1 for the entries of S2f / S2h, TGP_SUM_MAX for seam S2i, where the pair pass runs once per
+// term over the problems whose term t has the launch's evaluator, into partial sums of their own, and the fixed-order
+// reduction once per (problem, term); rows at or beyond a problem's term count are exactly 0.
+static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int T, int nb, const KSrc &ks, const int64_t *ns, int64_t nmax,
                             const double *X, const double *y, const double *yerr, double *logdet, double *ydota, double *grad,
                             int32_t *info) {
     if (!ctx) return -1;
-    if (!(ks && ns && X && y && logdet && grad && info)) {
+    if (!((ks.k1 || ks.ks) && ns && X && y && logdet && grad && info)) {
         ctx->err = std::string(fn) + ": ks, ns, X, y, logdet, grad and info must not be NULL";
         return -1;
     }
@@ -812,8 +988,8 @@ static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int nb, cons
     int rc = batch_begin(r, ctx, fn, nb, ks, ns, nmax, nullptr, logdet, ydota, info);
     if (rc) return rc;
     for (int b = 0; b < nb && !any; ++b)                    // (an unknown kind has been turned away by batch_begin)
-        if (kind_to_ke(ks[b].kind) != KE_GAUSS) {
-            ctx->err = std::string(fn) + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks[b].kind) +
+        if (kind_to_ke(ks.k1[b].kind) != KE_GAUSS) {
+            ctx->err = std::string(fn) + ": ks[" + std::to_string(b) + "].kind = " + std::to_string(ks.k1[b].kind) +
                        ": analytic derivatives exist for the Gaussian kernels only (RBF, AnisotropicRBF), as in the reference "
                        "(treegp/kernels.py:128-150)";
             return -1;
@@ -822,15 +998,15 @@ static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int nb, cons
     const BatchDims &d = r.d;
     const int64_t Np = d.Np, nP = Np / TGP_PW, nT = Np / TGP_TB;
     const GradDims g{Np / 64, nP};
-    // per problem beside S2e's arrays: Bt and C (Np x Np each), the reduction's partial sums, the four results
-    rc = batch_arena(r, 2 * rup((size_t)Np * Np * 8) + rup((size_t)(g.nrb * g.nP) * 32) + rup(32));
+    // per problem beside S2e's arrays: Bt and C (Np x Np each), the reduction's partial sums and the four results per term
+    rc = batch_arena(r, 2 * rup((size_t)Np * Np * 8) + rup((size_t)(T * g.nrb * g.nP) * 32) + rup((size_t)T * 32));
     if (rc) return rc;
     const int64_t C = r.C;
     BatchBufs &bb = r.bb;
     double *dBt = (double *)r.take((size_t)C * Np * Np * 8);
     double *dC = (double *)r.take((size_t)C * Np * Np * 8);
-    double *dpart = (double *)r.take((size_t)C * g.nrb * g.nP * 32);
-    double *dgrad = (double *)r.take((size_t)C * 32);
+    double *dpart = (double *)r.take((size_t)C * T * g.nrb * g.nP * 32);
+    double *dgrad = (double *)r.take((size_t)C * T * 32);
 
     for (int64_t c0 = 0; c0 < nb; c0 += C) {
         const int64_t cn = (nb - c0) < C ? (nb - c0) : C;
@@ -842,14 +1018,41 @@ static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int nb, cons
         batch_subst_identity(st, dBt, bb, d, ncn);
         bkinv_syrk_kernel<<<dim3((unsigned)(nT * (nT + 1) / 2), ncn), 256, 0, st>>>(dC, dBt, bb.dns, Np, (int)nP);
         const unsigned gw = (unsigned)(g.nrb * g.nP);
-        const int *cnt = bb.cnt, *start = bb.start;         // (all Gaussian: one launch over the identity list, b = blockIdx.y)
-        if (cnt[0]) bloglik_grad_kernel<KE_GAUSS><<<dim3(gw, cnt[0]), 256, 0, st>>>(bb.dkp, bb.dlist + start[0], bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
-        if (cnt[1]) bloglik_grad_kernel<KE_VK><<<dim3(gw, cnt[1]), 256, 0, st>>>(bb.dkp, bb.dlist + start[1], bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
-        if (cnt[2]) bloglik_grad_kernel<KE_AVK><<<dim3(gw, cnt[2]), 256, 0, st>>>(bb.dkp, bb.dlist + start[2], bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
-        bloglik_grad_reduce_kernel<<<ncn, 256, 0, st>>>(dpart, bb.dns, g, dgrad);
+        // the pair pass's launch lists: for every term t, the problems with more than t terms by the evaluator of their term t,
+        // each list in batch order (set t at t * cn of the table); one launch per list present
+        int gcnt[TGP_SUM_MAX][3], gstart[TGP_SUM_MAX][3], tmax = 0;
+        for (int t = 0; t < T; ++t) {
+            int *gl = bb.hglist + (int64_t)t * cn;
+            gcnt[t][0] = gcnt[t][1] = gcnt[t][2] = 0;
+            for (int64_t b = 0; b < cn; ++b)
+                if (t < bb.hks[b].nterms) ++gcnt[t][bb.hks[b].ke[t]];
+            gstart[t][0] = 0;
+            gstart[t][1] = gcnt[t][0];
+            gstart[t][2] = gcnt[t][0] + gcnt[t][1];
+            int fill[3] = {0, 0, 0};
+            for (int64_t b = 0; b < cn; ++b)
+                if (t < bb.hks[b].nterms) {
+                    const int k = bb.hks[b].ke[t];
+                    gl[gstart[t][k] + fill[k]++] = (int)b;
+                }
+            if (gcnt[t][0] + gcnt[t][1] + gcnt[t][2]) tmax = t + 1;
+        }
+        TGP_HIP(hipMemcpyAsync(bb.dglist, bb.hglist, (size_t)tmax * cn * 4, hipMemcpyHostToDevice, st));
+        if (T > 1) TGP_HIP(hipMemsetAsync(dgrad, 0, (size_t)cn * T * 32, st));       // rows >= nterms_b: exactly 0
+        for (int t = 0; t < tmax; ++t) {
+            const int *gl = bb.dglist + (int64_t)t * cn;
+#define TGP_PAIRS(KE, k)                                                                                                          \
+            if (gcnt[t][k])                                                                                                           \
+                bloglik_grad_kernel<KE><<<dim3(gw, gcnt[t][k]), 256, 0, st>>>(bb.dks, gl + gstart[t][k], t, T, bb.dns, bb.dX, bb.da, dC, Np, g, dpart);
+            TGP_PAIRS(KE_GAUSS, 0)
+            TGP_PAIRS(KE_VK, 1)
+            TGP_PAIRS(KE_AVK, 2)
+#undef TGP_PAIRS
+        }
+        bloglik_grad_reduce_kernel<<<dim3(ncn, (unsigned)tmax), 256, 0, st>>>(dpart, bb.dks, T, bb.dns, g, dgrad);
         TGP_HIP(hipGetLastError());
         TGP_HIP(hipEventRecord(ctx->ev[5], st));
-        rc = batch_end_chunk(r, c0, cn, grad + c0 * 4, dgrad, (size_t)cn * 32, 1);
+        rc = batch_end_chunk(r, c0, cn, grad + c0 * T * 4, dgrad, (size_t)cn * T * 32, 1);
         if (rc) return rc;
     }
     batch_finish(r);
@@ -858,24 +1061,29 @@ static int solve_grad_batch(tgp_ctx *ctx, const char *fn, bool any, int nb, cons
 
 int tgp_gp_solve_grad_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
                             const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
-    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch", false, nb, ks, ns, nmax, X, y, yerr, logdet, ydota, grad, info);
+    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch", false, 1, nb, KSrc{ks, nullptr}, ns, nmax, X, y, yerr, logdet, ydota, grad, info);
 }
 
 int tgp_gp_solve_grad_batch_any(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X,
                                 const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
-    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch_any", true, nb, ks, ns, nmax, X, y, yerr, logdet, ydota, grad, info);
+    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch_any", true, 1, nb, KSrc{ks, nullptr}, ns, nmax, X, y, yerr, logdet, ydota, grad, info);
+}
+
+int tgp_gp_solve_grad_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax, const double *X,
+                                const double *y, const double *yerr, double *logdet, double *ydota, double *grad, int32_t *info) {
+    return solve_grad_batch(ctx, "tgp_gp_solve_grad_batch_sum", true, TGP_SUM_MAX, nb, KSrc{nullptr, ks}, ns, nmax, X, y, yerr, logdet,
+                            ydota, grad, info);
 }
 
 // ---- S2g: diag(K^-1) of every problem of S2e from its factor, in the same call (leave-one-out, R&W 5.4.2) ----------------------
 // Per chunk, after batch_factor_chunk: Bt_b <- identity, the block substitution Bt_b <- L_b^-T over the live row tiles (the
 // launches of S2f), then one wave per row for |row i of Bt_b|^2 from the row's own panel on.  No C_b: half of S2f's flops behind
 // the solve, one Np x Np buffer per problem.
-int tgp_gp_loo_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X, const double *y,
-                     const double *yerr, double *alpha, double *invdiag, double *logdet, double *ydota, int32_t *info) {
-    static const char *fn = "tgp_gp_loo_batch";
+static int loo_batch(tgp_ctx *ctx, const char *fn, int nb, const KSrc &ks, const int64_t *ns, int64_t nmax, const double *X,
+                     const double *y, const double *yerr, double *alpha, double *invdiag, double *logdet, double *ydota, int32_t *info) {
     if (!ctx) return -1;
-    if (!(ks && ns && X && y && invdiag && logdet && info)) {
-        ctx->err = "tgp_gp_loo_batch: ks, ns, X, y, invdiag, logdet and info must not be NULL";
+    if (!((ks.k1 || ks.ks) && ns && X && y && invdiag && logdet && info)) {
+        ctx->err = std::string(fn) + ": ks, ns, X, y, invdiag, logdet and info must not be NULL";
         return -1;
     }
     BatchRun r;
@@ -908,4 +1116,15 @@ int tgp_gp_loo_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *
     }
     batch_finish(r);
     return 0;
+}
+
+int tgp_gp_loo_batch(tgp_ctx *ctx, int nb, const tgp_kernel *ks, const int64_t *ns, int64_t nmax, const double *X, const double *y,
+                     const double *yerr, double *alpha, double *invdiag, double *logdet, double *ydota, int32_t *info) {
+    return loo_batch(ctx, "tgp_gp_loo_batch", nb, KSrc{ks, nullptr}, ns, nmax, X, y, yerr, alpha, invdiag, logdet, ydota, info);
+}
+
+int tgp_gp_loo_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax, const double *X,
+                         const double *y, const double *yerr, double *alpha, double *invdiag, double *logdet, double *ydota,
+                         int32_t *info) {
+    return loo_batch(ctx, "tgp_gp_loo_batch_sum", nb, KSrc{nullptr, ks}, ns, nmax, X, y, yerr, alpha, invdiag, logdet, ydota, info);
 }

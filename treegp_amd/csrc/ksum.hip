@@ -11,23 +11,9 @@
 #include "tgp_internal.h"
 #include "kernel_eval.h"
 #include "kbuild_tile.h"
+#include "ksum_eval.h"
 
 namespace {
-struct KSumParams {
-    KParams t[TGP_SUM_MAX];
-    int ke[TGP_SUM_MAX];
-    double ampsum;            // ((amp_0 + amp_1) + ...): the exact diagonal of a self matrix
-    int nterms;
-    int any_vk;
-};
-
-// acc + v with v already rounded: the compiler must neither see the amplitude multiply behind v (it would contract
-// amp * k + acc into one FMA, and the element would no longer be the sum of the single-kernel values) nor fuse the add
-__device__ __forceinline__ double add_rounded(double acc, double v) {
-    asm volatile("" : "+v"(v));
-    return __dadd_rn(acc, v);
-}
-
 // the four values lane l owns in one row of a slab, term t added to them
 template <int KE>
 __device__ __forceinline__ void slab_row_add(const KParams &p, double xi, double yi, const double (&xj)[2][2],
@@ -195,24 +181,6 @@ __global__ __launch_bounds__(256) void sum_terms_kernel(const double *__restrict
     out[i] = v;
 }
 
-KSumParams make_ksum(const tgp_kernel_sum *k, bool slab_scaling) {
-    KSumParams ks;
-    memset(&ks, 0, sizeof(ks));
-    ks.nterms = k->nterms;
-    for (int t = 0; t < k->nterms; ++t) {
-        ks.t[t] = make_kparams(&k->term[t]);
-        ks.ke[t] = kind_to_ke(k->term[t].kind);
-        if (ks.ke[t] != KE_GAUSS) ks.any_vk = 1;
-        if (slab_scaling && ks.ke[t] == KE_GAUSS) {
-            const double c0 = 0.72134752044448170368;                        // 0.5 log2 e, as launch_kbuild_lower
-            ks.t[t].a *= c0;
-            ks.t[t].b2 *= c0;
-            ks.t[t].c *= c0;
-        }
-    }
-    ks.ampsum = tgp_ksum_amp(k);
-    return ks;
-}
 }  // namespace
 
 double tgp_ksum_amp(const tgp_kernel_sum *k) {

@@ -16,6 +16,10 @@ per route and releases them:
              forward differences with ``_FD_STEP`` (log_likelihood.py's scheme, the reference's iterates), the ntheta + 1
              points of every object in one ``ops.gp_solve_batch(want_alpha=False)``.
 
+Sums of up to four parametrised kernels (``kernels.kernel_to_sum_spec``) are eligible too: ``fd`` by default, as the single
+``solve()`` differences them, and with ``gradient="analytic-vk"`` the exact route through ``ops.gp_solve_grad_batch_sum`` (K^-1
+once per problem, the pair pass once per term) and ``kernels.sum_spec_jacobian``.
+
 L-BFGS-B keeps its state in the arrays of its own call, so an object's iterates are those of a fit run alone; objects that
 converge early drop out of the following calls.  All device calls are made by the calling thread.
 """
@@ -27,6 +31,7 @@ from scipy import optimize
 
 from . import _lib, ops
 from .gp_interp import _batch_spec
+from . import kernels as _kernels
 from .kernels import kernel_to_spec, spec_jacobian
 from .log_likelihood import log_likelihood, _BATCH_CALL, _FD_STEP
 
@@ -49,12 +54,15 @@ class _Fit(object):
         self.best = None
 
     def spec_at(self, theta):
-        """(KernelSpec, d(log amp, a, b, c) / d theta or None) at theta; None for a theta the kernel cannot take, which
-        counts as a rejected point as in ``log_likelihood.log_likelihood``"""
+        """(KernelSpec, d(log amp, a, b, c) / d theta or None) at theta -- for a sum (KernelSumSpec, d(log amp_t, a_t, b_t, c_t
+        for every term) / d theta or None); None for a theta the kernel cannot take, which counts as a rejected point as in
+        ``log_likelihood.log_likelihood``"""
         try:
             self.work.theta = theta
-            spec = kernel_to_spec(self.work)
-            if self.route == "analytic-vk":
+            spec = _device_spec(self.work)
+            if isinstance(spec, ops.KernelSumSpec):
+                jac = _kernels.sum_spec_jacobian(self.work) if self.route == "analytic-vk" else None
+            elif self.route == "analytic-vk":
                 jac = spec_jacobian(self.work, von_karman=True)
             else:
                 jac = spec_jacobian(self.work) if self.route == "analytic" else None
@@ -63,7 +71,14 @@ class _Fit(object):
         return spec, jac
 
 
+def _device_spec(kernel):
+    """what ``_batch_spec`` found for the object: ``kernel_to_spec``'s description, or else a sum's"""
+    return _kernels.device_spec(kernel, allow_sum=True, single=kernel_to_spec)
+
+
 def _has_analytic_gradient(kernel):
+    """the default exact route (``ops.gp_solve_grad_batch``): single Gaussian kernels; a sum keeps finite differences unless
+    ``gradient="analytic-vk"`` asks for the exact route of the sums, as in the single ``solve()``"""
     try:
         spec_jacobian(kernel)
         return kernel_to_spec(kernel).kind in (_lib.TGP_RBF, _lib.TGP_ARBF)
@@ -82,8 +97,9 @@ def _log_likelihoods(fits, specs):
 
 def _evaluate(requests):
     """{slot: (fit, theta)} -> {slot: (-log L, -d log L / d theta)}: one ``ops.gp_solve_grad_batch`` for the requests of the
-    analytic route, one ``ops.gp_solve_grad_batch_any`` for those of the analytic-vk route (all four kinds) and one
-    ``ops.gp_solve_batch`` for those of the finite-difference route."""
+    analytic route, one ``ops.gp_solve_grad_batch_any`` for those of the analytic-vk route (all four kinds;
+    ``ops.gp_solve_grad_batch_sum`` when a sum is among them) and one ``ops.gp_solve_batch`` for those of the finite-difference
+    route."""
     out = {}
     exact, exact_fits, exact_specs = [], [], []
     any_kind = False
@@ -115,6 +131,8 @@ def _evaluate(requests):
                 fd_specs.append(s[0])
     if exact:
         solve_grad_batch = ops.gp_solve_grad_batch_any if any_kind else ops.gp_solve_grad_batch
+        if any(isinstance(s, ops.KernelSumSpec) for s in exact_specs):
+            solve_grad_batch = ops.gp_solve_grad_batch_sum          # rows (nterms_b, 4) per problem, flattened for the chain rule
         log_det, chi2, g4, info = solve_grad_batch(exact_specs, [f.X for f in exact_fits], [f.y for f in exact_fits],
                                                    [f.y_err for f in exact_fits])
         for k, (slot, jac, ntheta) in enumerate(exact):
@@ -123,7 +141,7 @@ def _evaluate(requests):
             if info[k] != 0 or not np.isfinite(ll):
                 out[slot] = (np.inf, np.zeros(ntheta))
             else:
-                out[slot] = (-float(ll), -jac.dot(g4[k]))
+                out[slot] = (-float(ll), -jac.dot(np.ravel(g4[k])))
     if fd:
         lls = _log_likelihoods(fd_fits, fd_specs) if fd_specs else []
         for slot, points, ok, first in fd:
@@ -207,16 +225,19 @@ def _lockstep(fits):
 def solve_many(gps, gradient="auto"):
     """``for gp in gps: gp.solve()`` with the maximum-likelihood fits of many small GPs run in lockstep: one batched device call
     per optimiser iteration for all of them.  ``gps``: initialised GPInterpolation objects.  The objects with
-    ``optimizer="log-likelihood"`` whose kernel ``kernel_to_spec`` describes, that are not on the multi-GPU route and hold at
+    ``optimizer="log-likelihood"`` whose kernel ``kernels.device_spec`` describes (one parametrised kernel, or a sum of up to
+    four: "0.3**2 * AnisotropicVonKarman(...) + 0.5**2 * AnisotropicRBF(...)"), that are not on the multi-GPU route and hold at
     most 4096 points are fitted here, at most 256 at a time; afterwards each is in the state its own ``solve()`` leaves
     (``_init_theta``, the fitted ``kernel``, ``_optimizer`` with ``_kernel`` and ``_logL``, no cached solution).  Every other
     object then goes through its own ``solve()``, in list order.
 
     ``gradient``: "auto" (default) gives L-BFGS-B the exact gradient for the Gaussian kernels (RBF, AnisotropicRBF) and SciPy's
-    forward differences for the von Karman kinds; "fd" forward differences for every object, the reference's iterates;
+    forward differences for the von Karman kinds and for sums (what the single ``solve()`` does for them); "fd" forward
+    differences for every object, the reference's iterates;
     "analytic" raises NotImplementedError for an eligible object whose kernel has no analytic derivative; "analytic-vk" gives
-    every eligible object, the von Karman kinds included, the exact gradient (``ops.gp_solve_grad_batch_any``: a derivative the
-    reference does not have), one call per rendezvous."""
+    every eligible object, the von Karman kinds and sums included, the exact gradient (``ops.gp_solve_grad_batch_any``, or
+    ``ops.gp_solve_grad_batch_sum`` when a sum is among the objects: a derivative the reference does not have), one call per
+    rendezvous."""
     if gradient not in ("auto", "fd", "analytic", "analytic-vk"):
         raise ValueError("solve_many: gradient must be 'auto', 'fd', 'analytic' or 'analytic-vk', got %r" % (gradient,))
     gps = list(gps)
@@ -238,7 +259,7 @@ def solve_many(gps, gradient="auto"):
         group = fits[c0:c0 + _BATCH_CALL]
         _lockstep(group)
         fitted = [f.template.clone_with_theta(f.best) for f in group]
-        logls = _log_likelihoods(group, [kernel_to_spec(k) for k in fitted])
+        logls = _log_likelihoods(group, [_device_spec(k) for k in fitted])
         for f, kernel, logl in zip(group, fitted, logls):
             gp = f.gp
             gp._init_theta = [copy.deepcopy(f.template).theta]

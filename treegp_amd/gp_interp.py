@@ -529,8 +529,8 @@ class GPInterpolation(object):
 def predict_many(gps, Xs, return_cov=False, return_var=False):
     """``[gp.predict(X) for gp, X in zip(gps, Xs)]`` with the solves of many small GPs in one batched factorisation (the
     reference's regime: one GP per PSF parameter, exposure or chip, README.rst:28).  ``gps``: initialised GPInterpolation
-    objects; ``Xs``: their query points.  The objects whose kernel ``kernel_to_spec`` describes, that are not on the
-    multi-GPU route, hold at most 4096 points and have no cached solution get their alpha from one batched solve
+    objects; ``Xs``: their query points.  The objects whose kernel ``kernels.device_spec`` describes (one parametrised kernel
+    or a sum of up to four), that are not on the multi-GPU route, hold at most 4096 points and have no cached solution get their alpha from one batched solve
     (ops.gp_solve_batch); it is cached in ``gp._alpha`` as ``predict`` caches it, so that a later ``gp.predict`` reuses
     it.  Every object then predicts through its own ``predict``: the others solve there as usual.  A failed
     factorisation raises numpy.linalg.LinAlgError naming the object's index (nothing is cached then).
@@ -568,12 +568,13 @@ def predict_many(gps, Xs, return_cov=False, return_var=False):
 
 
 def _batch_spec(gp, kernel=None):
-    """the device kernel of an object the batched routes may take (kernel_to_spec describes it -- ``gp.kernel``, or the given
-    one -- not on the multi-GPU route, at most 4096 points), else None"""
+    """the device kernel of an object the batched routes may take (``kernels.device_spec`` describes it -- ``gp.kernel``, or the
+    given one: one parametrised kernel, ``ops.KernelSpec``, or a sum of up to four, ``ops.KernelSumSpec`` -- not on the multi-GPU
+    route, at most 4096 points), else None"""
     if gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX:
         return None
     try:
-        spec = kernel_to_spec(gp.kernel if kernel is None else kernel)
+        spec = _kernels.device_spec(gp.kernel if kernel is None else kernel, allow_sum=True, single=kernel_to_spec)
     except NotImplementedError:
         return None
     with gp._scope():
@@ -625,7 +626,7 @@ def _predict_many_posterior(gps, Xs, what):
 def predict_loo_many(gps, return_var=False):
     """``[gp.predict_loo(return_var) for gp in gps]`` with the factorisations and diag(K^-1) of many small GPs in one batched
     call (ops.gp_loo_batch): the validation step between ``solve_many`` and ``predict_many``.  The objects the batched routes
-    take (``kernel_to_spec`` describes the kernel, not on the multi-GPU route, at most 4096 points) and that hold no kept factor
+    take (``kernels.device_spec`` describes the kernel, not on the multi-GPU route, at most 4096 points) and that hold no kept factor
     of the same data go through it, then through ``loo_quantities`` on the host exactly as ``predict_loo``; a cached alpha is
     kept, an object without one caches the batch's, and no kept factor is left behind.  Every other object goes through its own
     ``predict_loo``.  A failed factorisation raises numpy.linalg.LinAlgError naming the object's index (nothing is cached

@@ -106,8 +106,8 @@ class log_likelihood(object):
 
     def log_likelihood_many(self, kernels):
         """One log L per kernel, each with exactly ``log_likelihood(kernel)``'s semantics (-inf for a matrix that is not
-        positive definite and for the failures that method turns into -inf).  The kernels ``kernel_to_spec`` describes go
-        through batched solves (ops.gp_solve_batch: one launch sequence for up to _BATCH_CALL of them); other kernel trees,
+        positive definite and for the failures that method turns into -inf).  The kernels ``kernels.device_spec`` describes
+        (one parametrised kernel, or a sum of up to four) go through batched solves (ops.gp_solve_batch: one launch sequence for up to _BATCH_CALL of them); other kernel trees,
         n > 4096 and the multi-GPU route take ``log_likelihood`` one kernel after the other."""
         kernels = list(kernels)
         out = np.full(len(kernels), -np.inf)
@@ -116,7 +116,7 @@ class log_likelihood(object):
             spec = None
             if not self.distributed and self.ndata <= ops.BATCH_NMAX:
                 try:
-                    spec = kernel_to_spec(kernel)
+                    spec = self._device_spec(kernel)
                 except NotImplementedError:
                     spec = None
             if spec is None:

@@ -33,6 +33,8 @@ class KernelSumSpec(object):
     entry is its single-kernel namesake, bit for bit).  ``kernel_matrix``, ``gp_solve``,
     ``gp_predict``, ``gp_predict_grad``, ``gp_predict_cov`` and ``gp_predict_var`` take it wherever they take a ``KernelSpec``
     and go to the ``_sum`` entries of include/tgp.h (seams S1s / S2s); ``gp_loglik_grad_sum`` is its likelihood gradient.
+    The batched calls ``gp_solve_batch``, ``gp_loo_batch`` and ``gp_posterior_batch`` take it among their kernels (seam S2i),
+    ``gp_solve_grad_batch_sum`` is the batched likelihood gradient and ``kbuild_batch`` returns what the batched K build stores.
     The multi-GPU engine does not take sums: these calls run on this process's GPU whatever the multi-GPU settings."""
     __slots__ = ("terms",)
 
@@ -194,12 +196,25 @@ def pad_batch(Xs, ys, y_errs=None):
     return ns, nmax, Xb, yb, eb
 
 
+def _batch_kernels(lib, name, specs):
+    """(entry, its name, the ctypes array of the kernels) of a batched call: the entry `name` with an array of tgp_kernel when
+    no spec is a ``KernelSumSpec`` -- the call of before sums existed -- else its `_sum` namesake (seam S2i of include/tgp.h)
+    with an array of tgp_kernel_sum, every ``KernelSpec`` wrapped as a sum of one term"""
+    nb = len(specs)
+    if not any(isinstance(s, KernelSumSpec) for s in specs):
+        ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+        return getattr(lib, name), name, C.cast(ks, C.c_void_p), ks
+    ks = (TgpKernelSum * nb)(*[(s if isinstance(s, KernelSumSpec) else KernelSumSpec([s])).to_c() for s in specs])
+    return getattr(lib, name + "_sum"), name + "_sum", ks, ks
+
+
 def gp_solve_batch(specs, Xs, ys, y_errs=None, want_alpha=True, ctx=None):
     """gp_solve for many independent small problems in one launch sequence (tgp_gp_solve_batch): problem b has kernel
     specs[b], coordinates Xs[b] (n_b, 1 or 2), values ys[b] (n_b,) and errors y_errs[b] (or none at all), n_b <= 4096.
     Returns (alphas: list of (n_b,) arrays or None, logdets (nb,), chi2 = y.alpha (nb,), info (nb,) int): info[b] > 0 is
     the order of the failing leading minor of problem b, whose other outputs are then meaningless.  Each problem's result
-    does not depend on the others in the call."""
+    does not depend on the others in the call.  ``specs`` may hold ``KernelSumSpec`` entries among the ``KernelSpec`` ones:
+    the call then goes to tgp_gp_solve_batch_sum; ``gp_loo_batch`` and ``gp_posterior_batch`` take them the same way."""
     specs = list(specs)
     ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
     nb = len(ns)
@@ -209,14 +224,13 @@ def gp_solve_batch(specs, Xs, ys, y_errs=None, want_alpha=True, ctx=None):
         raise ValueError("gp_solve_batch: problems of order up to %d, got %d (use gp_solve)" % (BATCH_NMAX, nmax))
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
-    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    fn, name, ks, _keep = _batch_kernels(lib, "tgp_gp_solve_batch", specs)
     alpha = np.empty((nb, nmax)) if want_alpha else None
     logdet = np.empty(nb)
     chi2 = np.empty(nb)
     info = np.zeros(nb, dtype=np.int32)
-    rc = lib.tgp_gp_solve_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(alpha),
-                                ptr(logdet), ptr(chi2), ptr(info))
-    check(ctx, rc, "tgp_gp_solve_batch")
+    rc = fn(ctx, nb, ks, ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(alpha), ptr(logdet), ptr(chi2), ptr(info))
+    check(ctx, rc, name)
     alphas = [alpha[b, :int(ns[b])].copy() for b in range(nb)] if want_alpha else None
     return alphas, logdet, chi2, info.astype(np.int64)
 
@@ -273,6 +287,59 @@ def gp_solve_grad_batch_any(specs, Xs, ys, y_errs=None, ctx=None):
     return logdet, chi2, g4, info.astype(np.int64)
 
 
+def _as_sum(spec):
+    return spec if isinstance(spec, KernelSumSpec) else KernelSumSpec([spec])
+
+
+def gp_solve_grad_batch_sum(specs, Xs, ys, y_errs=None, ctx=None):
+    """``gp_solve_grad_batch_any`` for sums of kernels (tgp_gp_solve_grad_batch_sum, seam S2i of include/tgp.h): ``specs`` holds
+    ``KernelSumSpec`` entries (a ``KernelSpec`` counts as a sum of one term), term counts and kinds mixed freely.  K^-1 is formed
+    once per problem and the pair pass runs once per term.  Returns (logdets (nb,), chi2 (nb,), grads, info (nb,) int) with
+    ``grads[b]`` of shape (nterms_b, 4): row t is d logL / d (log amp_t, a_t, b_t, c_t), what ``gp_loglik_grad_sum`` gives for
+    one problem; ``kernels.sum_spec_jacobian`` takes its flattened rows to theta."""
+    specs = [_as_sum(s) for s in specs]
+    ns, nmax, Xb, yb, eb = pad_batch(Xs, ys, y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("gp_solve_grad_batch_sum: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("gp_solve_grad_batch_sum: problems of order up to %d, got %d (use gp_solve and gp_loglik_grad_sum)"
+                         % (BATCH_NMAX, nmax))
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernelSum * nb)(*[s.to_c() for s in specs])
+    logdet = np.empty(nb)
+    chi2 = np.empty(nb)
+    g = np.empty((nb, _lib.TGP_SUM_MAX, 4))
+    info = np.zeros(nb, dtype=np.int32)
+    rc = lib.tgp_gp_solve_grad_batch_sum(ctx, nb, ks, ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(logdet), ptr(chi2), ptr(g),
+                                         ptr(info))
+    check(ctx, rc, "tgp_gp_solve_grad_batch_sum")
+    return logdet, chi2, [g[b, :len(specs[b].terms)].copy() for b in range(nb)], info.astype(np.int64)
+
+
+def kbuild_batch(specs, Xs, y_errs=None, ctx=None):
+    """What the batched K build stores (tgp_kbuild_batch_sum, the building block of seam S2i): for every problem the lower
+    triangle with its diagonal of K_b + diag(y_err_b^2) as an (n_b, n_b) array, exactly 0 above the diagonal.  ``specs``:
+    ``KernelSpec`` or ``KernelSumSpec`` entries; no factorisation runs.  The batched counterpart of the single build's
+    tgp_d_kbuild_lower + tgp_d_unpack_lower: it makes the stored values testable pair by pair."""
+    specs = [_as_sum(s) for s in specs]
+    Xs = list(Xs)
+    ns, nmax, Xb, _, eb = pad_batch(Xs, [np.zeros(len(X)) for X in Xs], y_errs)
+    nb = len(ns)
+    if len(specs) != nb:
+        raise ValueError("kbuild_batch: %d kernels for %d problems" % (len(specs), nb))
+    if nmax > BATCH_NMAX:
+        raise ValueError("kbuild_batch: problems of order up to %d, got %d" % (BATCH_NMAX, nmax))
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    ks = (TgpKernelSum * nb)(*[s.to_c() for s in specs])
+    K = np.empty((nb, nmax, nmax))
+    rc = lib.tgp_kbuild_batch_sum(ctx, nb, ks, ptr(ns), nmax, ptr(Xb), ptr(eb), ptr(K))
+    check(ctx, rc, "tgp_kbuild_batch_sum")
+    return [K[b, :int(ns[b]), :int(ns[b])].copy() for b in range(nb)]
+
+
 def gp_loo_batch(specs, Xs, ys, y_errs=None, ctx=None):
     """gp_solve_batch plus, from each problem's factor in the same call, d_b = diag((K_b + diag(y_err_b^2))^-1)
     (tgp_gp_loo_batch): with alpha, all that the leave-one-out quantities of a GP need (treegp_amd.loo).  Arguments as
@@ -289,15 +356,14 @@ def gp_loo_batch(specs, Xs, ys, y_errs=None, ctx=None):
                          % (BATCH_NMAX, nmax))
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
-    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    fn, name, ks, _keep = _batch_kernels(lib, "tgp_gp_loo_batch", specs)
     alpha = np.empty((nb, nmax))
     invdiag = np.empty((nb, nmax))
     logdet = np.empty(nb)
     chi2 = np.empty(nb)
     info = np.zeros(nb, dtype=np.int32)
-    rc = lib.tgp_gp_loo_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(alpha),
-                              ptr(invdiag), ptr(logdet), ptr(chi2), ptr(info))
-    check(ctx, rc, "tgp_gp_loo_batch")
+    rc = fn(ctx, nb, ks, ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(alpha), ptr(invdiag), ptr(logdet), ptr(chi2), ptr(info))
+    check(ctx, rc, name)
     alphas = [alpha[b, :int(ns[b])].copy() for b in range(nb)]
     invdiags = [invdiag[b, :int(ns[b])].copy() for b in range(nb)]
     return alphas, invdiags, logdet, chi2, info.astype(np.int64)
@@ -336,15 +402,15 @@ def gp_posterior_batch(specs, Xs, ys, y_errs, Xqs, what="var", want_alpha=True, 
         Xqb[b, :ms[b]] = Xq2[b]
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
-    ks = (TgpKernel * nb)(*[s.to_c() for s in specs])
+    fn, name, ks, _keep = _batch_kernels(lib, "tgp_gp_posterior_batch", specs)
     alpha = np.empty((nb, nmax)) if want_alpha else None
     unc = np.empty((nb, mmax, mmax) if what == "cov" else (nb, mmax))
     logdet = np.empty(nb)
     chi2 = np.empty(nb)
     info = np.zeros(nb, dtype=np.int32)
-    rc = lib.tgp_gp_posterior_batch(ctx, nb, C.cast(ks, C.c_void_p), ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(ms), mmax,
-                                    ptr(Xqb), 2 if what == "cov" else 1, ptr(alpha), ptr(unc), ptr(logdet), ptr(chi2), ptr(info))
-    check(ctx, rc, "tgp_gp_posterior_batch")
+    rc = fn(ctx, nb, ks, ptr(ns), nmax, ptr(Xb), ptr(yb), ptr(eb), ptr(ms), mmax, ptr(Xqb), 2 if what == "cov" else 1, ptr(alpha),
+            ptr(unc), ptr(logdet), ptr(chi2), ptr(info))
+    check(ctx, rc, name)
     alphas = [alpha[b, :int(ns[b])].copy() for b in range(nb)] if want_alpha else None
     # a problem with mmax points gets a view of the batch's array (no second copy of up to 128 MiB per covariance), the
     # others a compact copy of their block
