@@ -400,6 +400,46 @@ int tgp_gp_solve_grad_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, 
 int tgp_kbuild_batch_sum(tgp_ctx *ctx, int nb, const tgp_kernel_sum *ks, const int64_t *ns, int64_t nmax,
                          const double *X, const double *yerr, double *K);
 
+/* ---- S1, S2, S3 in three dimensions --------------------------------------------------------------------------------------------
+ * The reference's kernels take coordinates of any dimension (treegp/kernels.py:114-126, 355-381 hand pdist / cdist whatever invLam
+ * they are given; VonKarman and scikit-learn's RBF use Euclidean distances): position plus time, position plus colour.  These
+ * entries are their namesakes with X and Xs in (n, 3) / (m, 3) row-major and the kernel as a tgp_kernel3:
+ *   m       the upper triangle of the symmetric invLam, row-wise: xx, xy, xz, yy, yz, zz.  d^T invLam d is evaluated as
+ *           xx dx dx + 2xy dx dy + 2xz dx dz + yy dy dy + 2yz dy dz + zz dz dz from the differences d.  TGP_RBF: xx, yy, zz =
+ *           1 / l^2 per axis, the rest 0.  TGP_VK ignores m: u = |d| / ell.
+ * Only the launches that EVALUATE a kernel are the 3-D entries' own (nd3.hip): the packed K build (the layout, padding and exact
+ * diagonal amp + yerr_i^2 of S2), the dense kernel matrix (self: diagonal exactly amp), the fused mean and its gradient (the
+ * decomposition of S3 / S3g: 256 training points per LDS tile, partial sums per split, fixed-order reduce, no atomics; the
+ * Gaussian kinds through coordinates transformed once per call by the Cholesky factor of invLam, the direct quadratic form when
+ * invLam has none) and the cross panels of the posterior.  Factorisation, sweeps, substitution and products are the namesakes'
+ * launches: a factor kept by tgp_gp_solve3 is an ordinary tgp_factor, and tgp_factor_solve, _lmul, _inv_diag and _inv_blocks serve
+ * it unchanged.  The amplitude is multiplied after the transcendental; coincident points give exactly amp; a von Karman pair
+ * beyond 2 pi u > 697.87 is exactly 0; a pair at u == 0 contributes exactly 0 to the gradient; a NaN coordinate or parameter stays
+ * NaN.  tgp_gp_predict_grad3: gs is (m, 3).  tgp_gp_predict_var3 is the diagonal of tgp_gp_predict_cov3 (same panels, same
+ * substitution).  Arguments, limits, return codes and timings are the namesakes'; ndim != 3 or an unknown kind returns -1 with
+ * a message naming the entry and the field, before anything runs on the device.
+ * tgp_d_kbuild_lower3 is the building block, as tgp_d_kbuild_lower: d_X (n, 3) and d_A on the device; with tgp_d_unpack_lower it
+ * makes the stored values testable pair by pair.                                                                              */
+typedef struct {
+    int32_t kind;     /* TGP_RBF, TGP_ARBF, TGP_VK, TGP_AVK, meanings unchanged */
+    int32_t ndim;     /* 3 */
+    double amp;
+    double m[6];      /* invLam xx, xy, xz, yy, yz, zz (TGP_RBF: xx, yy, zz = 1 / l^2, the rest 0) */
+    double ell;       /* TGP_VK: u = |d| / ell */
+} tgp_kernel3;
+int tgp_kernel_matrix3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *Y, int64_t m, double *out);
+int tgp_d_kbuild_lower3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, const double *d_yerr, double *d_A);
+int tgp_gp_solve3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *y, const double *yerr,
+                  double *alpha, double *logdet, double *ydota, tgp_factor **keep);
+int tgp_gp_predict3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *alpha, const double *Xs,
+                    int64_t m, double *ys);
+int tgp_gp_predict_grad3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *alpha, const double *Xs,
+                         int64_t m, double *gs /* (m, 3) */);
+int tgp_gp_predict_cov3(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel3 *k, const double *X, int64_t n, const double *Xs,
+                        int64_t m, double *cov);
+int tgp_gp_predict_var3(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel3 *k, const double *X, int64_t n, const double *Xs,
+                        int64_t m, double *var);
+
 /* ---- S4: binned scalar pair correlation, exact binning -----------------------------------
  * w == NULL: unit weights.  TwoD: nbins x nbins pixels over [-max_sep, max_sep]^2, outputs
  * of length nbins^2 (flat index iy*nbins+ix).  Log: nbins log-spaced bins in

@@ -28,6 +28,11 @@ class TgpKernelSum(C.Structure):
     _fields_ = [("nterms", C.c_int32), ("_pad", C.c_int32), ("term", TgpKernel * TGP_SUM_MAX)]
 
 
+class TgpKernel3(C.Structure):
+    """tgp_kernel3 of include/tgp.h: m = invLam xx, xy, xz, yy, yz, zz"""
+    _fields_ = [("kind", C.c_int32), ("ndim", C.c_int32), ("amp", C.c_double), ("m", C.c_double * 6), ("ell", C.c_double)]
+
+
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -110,6 +115,14 @@ SIGNATURES = {
     "tgp_gp_loo_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_solve_grad_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_kbuild_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp]),
+    # seams S1, S2, S3 in three dimensions: each entry its namesake's prototype with a tgp_kernel3
+    "tgp_kernel_matrix3": (C.c_int, [_vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _i64, _vp]),
+    "tgp_d_kbuild_lower3": (C.c_int, [_vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _vp]),
+    "tgp_gp_solve3": (C.c_int, [_vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _vp, _vp, _dp, _dp, C.POINTER(_vp)]),
+    "tgp_gp_predict3": (C.c_int, [_vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tgp_gp_predict_grad3": (C.c_int, [_vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _vp, _i64, _vp]),
+    "tgp_gp_predict_cov3": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _i64, _vp]),
+    "tgp_gp_predict_var3": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel3), _vp, _i64, _vp, _i64, _vp]),
     "tgp_d_unpack_lower":(C.c_int, [_vp, _vp, _i64, _i64, _vp]),
     "tgp_factor_device": (C.c_int, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64)]),
     "tgp_debug_syrk_loop": (C.c_int, [_vp, _vp, _i64, C.c_int, _dp, _dp]),
@@ -294,6 +307,14 @@ def as_xy(X):
         X = np.hstack([X, np.zeros_like(X)])
     elif X.shape[1] != 2:
         raise ValueError("only 1-D and 2-D coordinates are supported, got ndim=%d" % X.shape[1])
+    return np.ascontiguousarray(X)
+
+
+def as_xyz(X):
+    """(n, 3) -> contiguous (n, 3) float64; anything else is a ValueError"""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != 3:
+        raise ValueError("3-D coordinates must have shape (n, 3), got %r" % (X.shape,))
     return np.ascontiguousarray(X)
 
 

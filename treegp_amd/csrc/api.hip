@@ -980,4 +980,140 @@ int tgp_gp_predict_grad_sum(tgp_ctx *ctx, const tgp_kernel_sum *k, const double 
     return predict_sum_from_host(ctx, k, X, n, alpha, Xs, m, 2, gs);
 }
 
+// ---- S1, S2, S3 in three dimensions: the namesakes above with (n, 3) coordinates and the launchers of nd3.hip -----------------
+int tgp_d_kbuild_lower3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, const double *d_yerr, double *d_A) {
+    if (tgp_kernel3_check(ctx, k, "tgp_d_kbuild_lower3")) return -1;
+    TGP_ARG(d_X && d_A && n > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    const int64_t Np = padded_n(n);
+    TGP_HIP(hipEventRecord(ctx->ev[0], ctx->stream));
+    int rc = launch_kbuild_lower3(ctx, k, d_X, n, Np, d_yerr, d_A);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[1], ctx->stream));
+    TGP_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->timings[0] = ms;
+    ctx->timings[8] = 8.0 * ((double)Np * (Np + 1) / 2.0) + 24.0 * (double)Np;
+    return 0;
+}
+
+// gp_solve_once with the 3-D K build; what follows the build is factor_and_solve, as for every other kernel
+static int gp_solve3_once(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, const double *d_y,
+                          const double *d_yerr, double *d_alpha, double *logdet, double *ydota, tgp_factor **keep) {
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t Np = padded_n(n);
+    int rc = ensure_factor_cache(ctx, Np);
+    if (rc) return rc;
+    double *d_A = ext_of(ctx)->A_cache;
+    rc = tgp_ensure_scratch(ctx, (size_t)Np * sizeof(double));
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    rc = launch_kbuild_lower3(ctx, k, d_X, n, Np, d_yerr, d_A);
+    if (rc) return rc;
+    static const bool no_augment = getenv("TGP_NO_AUGMENT") != nullptr || getenv("TGP_CHI2_BOTH_SWEEPS") != nullptr;
+    static const bool no_augment_alpha = getenv("TGP_NO_AUGMENT_ALPHA") != nullptr;
+    int S_unused = 0;
+    const bool augmented = !no_augment && keep == nullptr && n < Np &&
+                           (d_alpha == nullptr || (!no_augment_alpha && potrs_big_step(Np, &S_unused)));   // as gp_solve_once
+    if (augmented) {
+        rc = launch_augment_rhs(ctx, d_A, Np, n, d_y);
+        if (rc) return rc;
+    }
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    return factor_and_solve(ctx, n, Np, d_y, d_alpha, logdet, ydota, keep, augmented);
+}
+
+int tgp_gp_solve3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *y, const double *yerr,
+                  double *alpha, double *logdet, double *ydota, tgp_factor **keep) {
+    if (tgp_kernel3_check(ctx, k, "tgp_gp_solve3")) return -1;
+    TGP_ARG(X && y && n > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    int rc = ensure_io(ctx, rup(3 * n * 8) + 3 * rup(n * 8));
+    if (rc) return rc;
+    rc = ensure_hio(ctx, rup(3 * n * 8) + 3 * rup(n * 8));
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_X = ar.take<double>(3 * n), *d_y = ar.take<double>(n), *d_e = ar.take<double>(n), *d_a = ar.take<double>(n);
+    TGP_HIP(h2d(ctx, d_X, X, 3 * n * 8));
+    TGP_HIP(h2d(ctx, d_y, y, n * 8));
+    if (yerr) TGP_HIP(h2d(ctx, d_e, yerr, n * 8));
+    {
+        SolveInFlight here;                                  // as tgp_d_gp_solve: in-kernel hand-offs only for a solve that is alone
+        ctx->mid_allowed = here.alone ? 1 : 0;
+        rc = gp_solve3_once(ctx, k, d_X, n, d_y, yerr ? d_e : nullptr, alpha ? d_a : nullptr, logdet, ydota, keep);
+        ctx->mid_allowed = 0;
+        if (rc == TGP_RC_HANDOFF && !ctx->mid_off) {
+            ctx->mid_off = 1;
+            rc = gp_solve3_once(ctx, k, d_X, n, d_y, yerr ? d_e : nullptr, alpha ? d_a : nullptr, logdet, ydota, keep);
+        }
+    }
+    if (rc) return rc;
+    if (alpha) TGP_HIP(d2h_sync(ctx, alpha, d_a, n * 8));
+    return 0;
+}
+
+// width = 1: tgp_gp_predict3, 3: tgp_gp_predict_grad3
+static int predict3_from_host(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *alpha,
+                              const double *Xs, int64_t m, int width, double *out) {
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t io_bytes = rup(3 * n * 8) + rup(n * 8) + rup(3 * m * 8) + rup((size_t)width * m * 8);
+    int rc = ensure_io(ctx, io_bytes);
+    if (rc) return rc;
+    rc = ensure_hio(ctx, io_bytes);
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_X = ar.take<double>(3 * n), *d_a = ar.take<double>(n), *d_Xs = ar.take<double>(3 * m),
+           *d_out = ar.take<double>((size_t)width * m);
+    TGP_HIP(h2d(ctx, d_X, X, 3 * n * 8));
+    TGP_HIP(h2d(ctx, d_a, alpha, n * 8));
+    TGP_HIP(h2d(ctx, d_Xs, Xs, 3 * m * 8));
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    rc = width == 1 ? launch_predict3(ctx, k, d_X, n, d_a, d_Xs, m, d_out) : launch_predict_grad3(ctx, k, d_X, n, d_a, d_Xs, m, d_out);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    TGP_HIP(d2h_sync(ctx, out, d_out, (size_t)width * m * 8));
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->timings[3] = ms;
+    return 0;
+}
+
+int tgp_gp_predict3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *alpha, const double *Xs,
+                    int64_t m, double *ys) {
+    if (tgp_kernel3_check(ctx, k, "tgp_gp_predict3")) return -1;
+    TGP_ARG(X && alpha && Xs && ys && n > 0 && m > 0);
+    return predict3_from_host(ctx, k, X, n, alpha, Xs, m, 1, ys);
+}
+
+int tgp_gp_predict_grad3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *alpha, const double *Xs,
+                         int64_t m, double *gs) {
+    if (tgp_kernel3_check(ctx, k, "tgp_gp_predict_grad3")) return -1;
+    TGP_ARG(X && alpha && Xs && gs && n > 0 && m > 0);
+    return predict3_from_host(ctx, k, X, n, alpha, Xs, m, 3, gs);
+}
+
+int tgp_kernel_matrix3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *X, int64_t n, const double *Y, int64_t m, double *out) {
+    if (tgp_kernel3_check(ctx, k, "tgp_kernel_matrix3")) return -1;
+    TGP_ARG(X && out && n > 0);
+    const int self = (Y == nullptr);
+    if (self) m = n;
+    TGP_ARG(m > 0);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = ensure_io(ctx, rup(3 * n * 8) + rup(3 * m * 8) + rup((size_t)n * m * 8));
+    if (rc) return rc;
+    Arena ar{(char *)ext_of(ctx)->io.buf};
+    double *d_X = ar.take<double>(3 * n), *d_Y = ar.take<double>(3 * m), *d_o = ar.take<double>((size_t)n * m);
+    TGP_HIP(hipMemcpyAsync(d_X, X, 3 * n * 8, hipMemcpyHostToDevice, st));
+    if (!self) TGP_HIP(hipMemcpyAsync(d_Y, Y, 3 * m * 8, hipMemcpyHostToDevice, st));
+    rc = launch_kernel_dense3(ctx, k, d_X, n, self ? d_X : d_Y, m, self, d_o);
+    if (rc) return rc;
+    TGP_HIP(hipMemcpyAsync(out, d_o, (size_t)n * m * 8, hipMemcpyDeviceToHost, st));
+    TGP_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 }  // extern "C"

@@ -103,21 +103,21 @@ struct CovPlan {
     double *d_X, *d_Xs, *d_Bt, *d_C, *d_v, *d_kss;
     int64_t c0 = 0;
 };
-int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan *pl, int64_t var_rows = 0) {
+int cov_plan(tgp_ctx *ctx, const tgp_factor *f, int64_t m, bool coords, CovPlan *pl, int64_t var_rows = 0, int cdim = 2) {   // cdim: columns of the coordinates
     pl->n = f->n; pl->m = m; pl->Np = f->Np;
     pl->nP = (int)(pl->Np / TGP_PW);
     pl->Mp = var_rows ? var_rows : (m + TGP_PW - 1) / TGP_PW * TGP_PW;   // 256: the covariance uses the panel layout too
     pl->nPm = (int)(pl->Mp / TGP_PW);
     TGP_ARG(pl->Mp <= 65535 && pl->Mp % TGP_PW == 0);
     const size_t tail = var_rows ? 2 * rup((size_t)pl->Mp * 8) : rup((size_t)pl->Mp * pl->Mp * 8);
-    const size_t need = (coords ? rup(2 * pl->n * 8) + rup(2 * m * 8) : 0) + rup((size_t)pl->Mp * pl->Np * 8) + tail;
+    const size_t need = (coords ? rup((size_t)cdim * pl->n * 8) + rup((size_t)cdim * m * 8) : 0) + rup((size_t)pl->Mp * pl->Np * 8) + tail;
     int rc = tgp_ensure_scratch(ctx, need);
     if (rc) return rc;
     char *base = (char *)ctx->scratch;
     size_t off = 0;
     auto take = [&](size_t b) { char *p = base + off; off += rup(b); return (double *)p; };
-    pl->d_X = coords ? take(2 * pl->n * 8) : nullptr;
-    pl->d_Xs = coords ? take(2 * m * 8) : nullptr;
+    pl->d_X = coords ? take((size_t)cdim * pl->n * 8) : nullptr;
+    pl->d_Xs = coords ? take((size_t)cdim * m * 8) : nullptr;
     pl->d_Bt = take((size_t)pl->Mp * pl->Np * 8);
     pl->d_C = var_rows ? nullptr : take((size_t)pl->Mp * pl->Mp * 8);
     pl->d_v = var_rows ? take((size_t)pl->Mp * 8) : nullptr;
@@ -351,6 +351,47 @@ extern "C" int tgp_gp_predict_var(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel 
     // k(x_i, x_i) of the four parametrised kinds is exactly amp (the self kernel's diagonal, tgp_kernel_matrix)
     return var_chunks(ctx, f, pl, Mc, k->amp, false, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows, int) {
         return launch_cross_panels(ctx, k, cp.d_Xs + 2 * r0, rows, cp.d_X, n, 0, cp.d_Bt, cp.Mp, cp.Np);
+    });
+}
+
+// ---- S3b / S3c in three dimensions: the two entries above with (n, 3) coordinates and the cross panels of nd3.hip; substitution,
+// products and row norms are the same launches, so var3 is the diagonal of cov3 as var is of cov
+extern "C" int tgp_gp_predict_cov3(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel3 *k, const double *X, int64_t n,
+                                   const double *Xs, int64_t m, double *cov) {
+    if (tgp_kernel3_check(ctx, k, "tgp_gp_predict_cov3")) return -1;
+    TGP_ARG(f && X && Xs && cov && m > 0 && n == f->n);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    CovPlan pl;
+    int rc = cov_plan(ctx, f, m, true, &pl, 0, 3);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(pl.d_X, X, 3 * n * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(pl.d_Xs, Xs, 3 * m * 8, hipMemcpyHostToDevice, st));
+    rc = launch_cross_panels3(ctx, k, pl.d_Xs, m, pl.d_X, n, 0, pl.d_Bt, pl.Mp, pl.Np);
+    if (rc) return rc;
+    rc = launch_cross_panels3(ctx, k, pl.d_Xs, m, pl.d_Xs, m, 1, pl.d_C, pl.Mp, pl.Mp);
+    if (rc) return rc;
+    return cov_finish(ctx, f, pl, cov);
+}
+
+extern "C" int tgp_gp_predict_var3(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel3 *k, const double *X, int64_t n,
+                                   const double *Xs, int64_t m, double *var) {
+    if (tgp_kernel3_check(ctx, k, "tgp_gp_predict_var3")) return -1;
+    TGP_ARG(f && X && Xs && var && m > 0 && n == f->n);
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int64_t Mc = 0;
+    int rc = var_chunk_rows(ctx, f, m, &Mc);
+    if (rc) return rc;
+    CovPlan pl;
+    rc = cov_plan(ctx, f, m, true, &pl, Mc, 3);
+    if (rc) return rc;
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(pl.d_X, X, 3 * n * 8, hipMemcpyHostToDevice, st));
+    TGP_HIP(hipMemcpyAsync(pl.d_Xs, Xs, 3 * m * 8, hipMemcpyHostToDevice, st));
+    return var_chunks(ctx, f, pl, Mc, k->amp, false, false, var, [&](const CovPlan &cp, int64_t r0, int64_t rows, int) {
+        return launch_cross_panels3(ctx, k, cp.d_Xs + 3 * r0, rows, cp.d_X, n, 0, cp.d_Bt, cp.Mp, cp.Np);
     });
 }
 

@@ -360,7 +360,16 @@ __global__ __launch_bounds__(256) void predict_grad_reduce_kernel(const double *
     gs[2 * q] = r00 * s0;
     gs[2 * q + 1] = (r10 == 0.0) ? r11 * s1 : r10 * s0 + r11 * s1;
 }
+// the 2^(j/256) table above into a caller's buffer of 256 doubles, for the 3-D Gaussian fast path (nd3.hip stages that copy in LDS
+// as the kernels here stage the table itself; the table stays a symbol of this file alone)
+__global__ __launch_bounds__(256) void exp2_j256_copy_kernel(double *__restrict__ out) { out[threadIdx.x] = EXP2_J256[threadIdx.x]; }
 }  // namespace
+
+int launch_exp2_j256_copy(tgp_ctx *ctx, double *d_out) {
+    exp2_j256_copy_kernel<<<1, 256, 0, ctx->stream>>>(d_out);
+    TGP_HIP(hipGetLastError());
+    return 0;
+}
 
 int launch_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
                    const double *d_Xs, int64_t m, double *d_ys) {

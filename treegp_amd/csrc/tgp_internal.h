@@ -284,6 +284,20 @@ int launch_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t
 // gradient of the predicted mean with respect to the query point: d_gs (m, 2)
 int launch_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *d_X, int64_t n, const double *d_alpha,
                         const double *d_Xs, int64_t m, double *d_gs);
+// nd3.hip: the kernel-evaluating launches for (n, 3) coordinates (seams S1 - S3 in three dimensions).  tgp_kernel3_check: -1 with
+// a message naming `fn` and the field for ndim != 3 or an unknown kind; the launchers expect a checked kernel.
+int launch_exp2_j256_copy(tgp_ctx *ctx, double *d_out);           // predict.hip: 2^(j/256), j = 0 .. 255, into d_out[256]
+int tgp_kernel3_check(tgp_ctx *ctx, const tgp_kernel3 *k, const char *fn);
+int launch_kbuild_lower3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, int64_t Np, const double *d_yerr,
+                         double *d_A);
+int launch_kernel_dense3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, const double *d_Y, int64_t m, int self,
+                         double *d_out);
+int launch_predict3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, const double *d_alpha, const double *d_Xs,
+                    int64_t m, double *d_ys);
+int launch_predict_grad3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_X, int64_t n, const double *d_alpha,
+                         const double *d_Xs, int64_t m, double *d_gs);
+int launch_cross_panels3(tgp_ctx *ctx, const tgp_kernel3 *k, const double *d_Xs, int64_t m, const double *d_X, int64_t n, int self,
+                         double *d_out, int64_t rows, int64_t ncols);
 int launch_unpack_lower(tgp_ctx *ctx, const double *d_A, int64_t Np, int64_t n, double *d_out);
 int launch_pack_lower(tgp_ctx *ctx, const double *d_K, int64_t n, int64_t Np, const double *d_yerr, double *d_A);
 // d_B: (nrhs, Np) right-hand sides, solved in place, the factor read once per sweep for groups of up to 8 of them

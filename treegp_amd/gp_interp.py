@@ -19,8 +19,16 @@ from .kernels import eval_kernel, kernel_to_spec
 from .loo import group_runs, lgo_quantities, loo_quantities
 
 
+def _three_d(X):
+    """coordinates with three columns: the ``3`` entries of include/tgp.h (ops.KernelSpec3)"""
+    return np.ndim(X) == 2 and np.shape(X)[1] == 3
+
+
 class GPInterpolation(object):
-    """Gaussian-process interpolation of one scalar field over 1-D / 2-D coordinates.
+    """Gaussian-process interpolation of one scalar field over 1-D / 2-D / 3-D coordinates.  3-D coordinates (position plus
+    time, position plus colour) take the device route by themselves for the four parametrised kernels (``kernels.kernel_to_spec3``)
+    with ``optimizer`` "none" or "log-likelihood"; the 2-point-correlation optimisers and a mean-function table are 2-D
+    statistics and raise ValueError for them.
 
     :param kernel:        string that ``eval_kernel`` turns into a scikit-learn kernel. [default 'RBF(1)']
     :param optimizer:     "none", "two-pcf", "anisotropic" or "log-likelihood".
@@ -115,6 +123,12 @@ class GPInterpolation(object):
         ``n`` points (this object's backend included), sums keep the dense route too."""
         with self._scope():
             multi_gpu = ops._dist_engine(len(self._X) if n is None else n, None) is not None
+        if _three_d(self._X):
+            # ops.KernelSpec3; the multi-GPU engine has no 3-D K build and sums of 3-D kernels no device form: the dense route,
+            # where the kernel object evaluates itself through ops.kernel_matrix
+            if multi_gpu:
+                raise NotImplementedError("3-D coordinates keep the dense route under the multi-GPU engine")
+            return _kernels.device_spec(kernel, ndim=3)
         return _kernels.device_spec(kernel, allow_sum=not multi_gpu, single=kernel_to_spec)
 
     @staticmethod
@@ -122,6 +136,9 @@ class GPInterpolation(object):
         import hashlib
         h = hashlib.blake2b(digest_size=16)
         for term in getattr(spec, "terms", [spec]):          # a sum: every term
+            if isinstance(term, ops.KernelSpec3):
+                h.update(np.asarray((3.0, term.kind, term.amp, term.ell) + term.m, dtype=np.float64).tobytes())
+                continue
             h.update(np.asarray([term.kind, term.amp, term.a, term.b, term.c, term.ell], dtype=np.float64).tobytes())
         for arr in (X1, y_err):
             arr = np.ascontiguousarray(arr, dtype=np.float64)
@@ -215,7 +232,7 @@ class GPInterpolation(object):
         return y_predict, None
 
     def predict_gradient(self, X):
-        """Spatial derivative of the interpolated field at X (n_samples, 1 or 2): (n_samples, ndim), column c the derivative
+        """Spatial derivative of the interpolated field at X (n_samples, 1, 2 or 3): (n_samples, ndim), column c the derivative
         along coordinate c of the GP part of what ``predict(X)`` returns, from the kernel's analytic derivative
         (ops.gp_predict_grad) instead of differences of ``predict`` at shifted points.  Not in the reference.  The constant
         ``_mean`` of ``normalize`` drops out; a KNN mean function is piecewise constant and contributes nothing (its jumps
@@ -224,15 +241,15 @@ class GPInterpolation(object):
         Kernels of the dense route (anything ``kernels.device_spec`` does not describe: one parametrised kernel or a sum of up
         to four) have no device form of their derivative: NotImplementedError.  Runs on one GPU whichever backend solved."""
         try:
-            spec = _kernels.device_spec(self.kernel, single=kernel_to_spec)
+            spec = _kernels.device_spec(self.kernel, single=kernel_to_spec, ndim=3 if _three_d(self._X) else 2)
         except NotImplementedError:
             raise NotImplementedError("predict_gradient needs a kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
                                       "AnisotropicVonKarman, optionally times a constant, or a sum of up to four of those); "
                                       "got %r" % (self.kernel,))
         with self._scope():
             solve_spec = spec
-            if isinstance(spec, ops.KernelSumSpec) and ops._dist_engine(len(self._X), None) is not None:
-                solve_spec = None                               # a sum under the multi-GPU engine is solved on the dense route
+            if isinstance(spec, (ops.KernelSumSpec, ops.KernelSpec3)) and ops._dist_engine(len(self._X), None) is not None:
+                solve_spec = None                               # a sum or a 3-D object under the multi-GPU engine is solved on the dense route
             self._ensure_solution(self._residual(), self._X, self.kernel, solve_spec, self._y_err, want_factor=False)
         ndim = 1 if np.ndim(X) < 2 else np.shape(X)[1]
         return ops.gp_predict_grad(spec, self._X, self._alpha, X)[:, :ndim]
@@ -462,9 +479,12 @@ class GPInterpolation(object):
 
     # -- data ------------------------------------------------------------------------------------
     def initialize(self, X, y, y_err=None):
-        """Take the data: coordinates (n, 1 or 2), values, errors (zeros when None).  gp_interp.py:196-227:
+        """Take the data: coordinates (n, 1, 2 or 3), values, errors (zeros when None).  gp_interp.py:196-227:
         a fresh copy of the kernel template, white noise added to the errors in quadrature, the mean taken
         of y minus the mean function, any cached solution dropped."""
+        if _three_d(X) and self._X0 is not None and np.count_nonzero(self._X0) > 0:
+            raise ValueError("a mean-function table is a 2-D statistic (meanify bins the first two coordinates); it cannot be "
+                             "used with 3-D coordinates, got X of shape %r" % (np.shape(X),))
         self.kernel = copy.deepcopy(self.kernel_template)
         self._X, self._y = X, y
         sigma = np.zeros_like(y) if y_err is None else y_err
@@ -501,6 +521,9 @@ class GPInterpolation(object):
     def solve(self):
         """Fit the hyper-parameters if an optimizer was requested (gp_interp.py:245-258); the starting theta
         is kept in ``_init_theta``."""
+        if _three_d(self._X) and self.optimizer in ("two-pcf", "anisotropic"):
+            raise ValueError("optimizer=%r fits a 2-D statistic (the 2-point correlation function of the first two coordinates); "
+                             "3-D coordinates take optimizer='log-likelihood' or 'none'" % (self.optimizer,))
         self._init_theta = [copy.deepcopy(self.kernel).theta]
         with self._scope():
             self.kernel = self._fit(self.kernel, self._X, self._residual(), self._y_err)
@@ -571,8 +594,8 @@ def _batch_spec(gp, kernel=None):
     """the device kernel of an object the batched routes may take (``kernels.device_spec`` describes it -- ``gp.kernel``, or the
     given one: one parametrised kernel, ``ops.KernelSpec``, or a sum of up to four, ``ops.KernelSumSpec`` -- not on the multi-GPU
     route, at most 4096 points), else None"""
-    if gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX:
-        return None
+    if gp.backend == "dist" or len(gp._X) > ops.BATCH_NMAX or _three_d(gp._X):
+        return None                               # (a 3-D object is one of the "other objects": there is no batched 3-D build)
     try:
         spec = _kernels.device_spec(gp.kernel if kernel is None else kernel, allow_sum=True, single=kernel_to_spec)
     except NotImplementedError:

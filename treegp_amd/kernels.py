@@ -103,6 +103,8 @@ class _CholeskyParametrised(StationaryKernelMixin, NormalizedKernelMixin, Kernel
 
     # -- evaluation ------------------------------------------------------------------------
     def _spec(self):
+        if self.ndim == 3:
+            return _invlam_spec3(self._tgp_kind, self.invLam, 1.0)
         return _invlam_spec(self._tgp_kind, self.invLam, 1.0)
 
     def __call__(self, X, Y=None, eval_gradient=False):
@@ -132,7 +134,7 @@ class _CholeskyParametrised(StationaryKernelMixin, NormalizedKernelMixin, Kernel
 class AnisotropicRBF(_CholeskyParametrised):
     """exp(-0.5 (x-x')^T invLam (x-x'))  -- treegp/kernels.py:62-186.
 
-    :param invLam:        inverse covariance matrix (ndim x ndim, ndim in {1, 2} on the GPU).
+    :param invLam:        inverse covariance matrix (ndim x ndim, ndim in {1, 2, 3} on the GPU).
     :param scale_length:  axis-aligned scale lengths instead of invLam (exactly one of the two).
     :param bounds:        bounds on theta, (2,) or (ntheta, 2).
     """
@@ -181,16 +183,20 @@ class VonKarman(StationaryKernelMixin, NormalizedKernelMixin, Kernel):
         count = len(self.length_scale) if self.anisotropic else 1
         return Hyperparameter("length_scale", "numeric", self.length_scale_bounds, count)
 
-    def _spec(self):
+    def _spec(self, ndim=2):
+        """the device description for coordinates of `ndim` columns (the kernel itself carries no dimension)"""
         if self.anisotropic:
             raise NotImplementedError("per-axis length scales are not defined for VonKarman distances")
-        return ops.KernelSpec(_lib.TGP_VK, amp=1.0, ell=float(np.ravel(self.length_scale)[0]))
+        ell = float(np.ravel(self.length_scale)[0])
+        if ndim == 3:
+            return ops.KernelSpec3(_lib.TGP_VK, amp=1.0, ell=ell)
+        return ops.KernelSpec(_lib.TGP_VK, amp=1.0, ell=ell)
 
     def __call__(self, X, Y=None, eval_gradient=False):
         X = np.atleast_2d(X)
         if eval_gradient and Y is not None:
             raise ValueError("Gradient can only be evaluated when Y is None.")
-        K = ops.kernel_matrix(self._spec(), X, None if Y is None else np.atleast_2d(Y))
+        K = ops.kernel_matrix(self._spec(3 if X.shape[1] == 3 else 2), X, None if Y is None else np.atleast_2d(Y))
         if not eval_gradient:
             return K
         # what the reference returns (kernels.py:278-288): K times the Euclidean distances -- not dK/d log l, reproduced as is
@@ -252,6 +258,48 @@ def kernel_to_spec(kernel):
     raise NotImplementedError("kernel %r is not supported by the GPU hot path" % (kernel,))
 
 
+def _invlam_spec3(kind, invLam, amp):
+    """``ops.KernelSpec3`` of a 3 x 3 invLam; a non-symmetric one is averaged, as ``_invlam_spec`` does"""
+    invLam = np.asarray(invLam, dtype=np.float64)
+    if invLam.shape != (3, 3):
+        raise NotImplementedError("a 3-D kernel needs a 3 x 3 invLam, got shape %r" % (invLam.shape,))
+    sym = 0.5 * (invLam + invLam.T)
+    return ops.KernelSpec3(kind, amp=amp, m=(invLam[0, 0], sym[0, 1], sym[0, 2], invLam[1, 1], sym[1, 2], invLam[2, 2]))
+
+
+def kernel_to_spec3(kernel):
+    """``ops.KernelSpec3`` (kind, amp, m = invLam xx, xy, xz, yy, yz, zz, ell) for the trees ``kernel_to_spec`` accepts, over
+    (n, 3) coordinates: [ConstantKernel *]* one of RBF (one or three length scales) / AnisotropicRBF / AnisotropicVonKarman
+    (3 x 3 invLam) / VonKarman.  Anything else raises NotImplementedError -- there is no silent host fallback."""
+    amp = 1.0
+    node = kernel
+    while isinstance(node, Product):
+        if isinstance(node.k1, ConstantKernel):
+            amp *= float(node.k1.constant_value)
+            node = node.k2
+        elif isinstance(node.k2, ConstantKernel):
+            amp *= float(node.k2.constant_value)
+            node = node.k1
+        else:
+            raise NotImplementedError("only ConstantKernel * <stationary kernel> products run on the GPU, got %r" % (kernel,))
+    if isinstance(node, AnisotropicRBF):
+        return _invlam_spec3(_lib.TGP_ARBF, node.invLam, amp)
+    if isinstance(node, AnisotropicVonKarman):
+        return _invlam_spec3(_lib.TGP_AVK, node.invLam, amp)
+    if isinstance(node, VonKarman):
+        s = node._spec(3)
+        s.amp = amp
+        return s
+    if type(node) is RBF:                       # exactly RBF: scikit-learn's Matern derives from it
+        ls = np.ravel(np.asarray(node.length_scale, dtype=np.float64))
+        if ls.size == 1:
+            ls = np.repeat(ls, 3)
+        if ls.size != 3:
+            raise NotImplementedError("RBF over 3-D coordinates needs one or three length scales, got %d" % ls.size)
+        return ops.KernelSpec3(_lib.TGP_RBF, amp=amp, m=(1.0 / ls[0] ** 2, 0.0, 0.0, 1.0 / ls[1] ** 2, 0.0, 1.0 / ls[2] ** 2))
+    raise NotImplementedError("kernel %r is not supported by the GPU hot path" % (kernel,))
+
+
 def _sum_leaves(kernel):
     """the terms of a (nested) scikit-learn Sum in its own order, k1 before k2"""
     if isinstance(kernel, Sum):
@@ -273,12 +321,16 @@ def kernel_to_sum_spec(kernel):
     return ops.KernelSumSpec([kernel_to_spec(leaf) for leaf in leaves])
 
 
-def device_spec(kernel, allow_sum=True, single=None):
+def device_spec(kernel, allow_sum=True, single=None, ndim=2):
     """The device description of a kernel for the single-problem routes: ``kernel_to_spec``'s ``ops.KernelSpec``, or else
     ``kernel_to_sum_spec``'s ``ops.KernelSumSpec``; NotImplementedError for every other tree (the dense route).
     ``allow_sum=False``: sums raise too (the multi-GPU engine has no sum-aware K build: they keep the dense route there).
     ``single``: the caller's own ``kernel_to_spec`` name, so that the modules' call sites keep resolving single kernels
-    through the name they import (their tests stand in for it there)."""
+    through the name they import (their tests stand in for it there).
+    ``ndim``: the number of columns of the coordinates (the isotropic kernels carry none).  ``ndim == 3``: ``kernel_to_spec3``'s
+    ``ops.KernelSpec3``; sums of 3-D kernels raise NotImplementedError whatever ``allow_sum`` says (they keep the dense route)."""
+    if ndim == 3:
+        return kernel_to_spec3(kernel)
     try:
         return (single or kernel_to_spec)(kernel)
     except NotImplementedError:

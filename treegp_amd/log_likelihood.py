@@ -55,11 +55,14 @@ def _rejects_theta(ex):
 
 
 class log_likelihood(object):
-    """:param X: coordinates (n_samples, 1 or 2)  :param y: values  :param y_err: errors."""
+    """:param X: coordinates (n_samples, 1, 2 or 3)  :param y: values  :param y_err: errors."""
 
     def __init__(self, X, y, y_err):
         self.X, self.y, self.y_err = X, y, y_err
         self.ndata = len(X[:, 0])
+        # 3-D coordinates: every evaluation is one ops.gp_solve with a KernelSpec3 (no resident data, no batched solve, no exact
+        # gradient: the fit differences the likelihood at every size, as the reference does)
+        self.three_d = np.ndim(X) == 2 and np.shape(X)[1] == 3
         # the multi-GPU route (treegp_amd.dist) takes every evaluation by itself: all ranks factorise one K together
         self.distributed = ops._dist_engine(self.ndata, None) is not None
         self.parallel_fd = (os.environ.get("TGP_ML_PARALLEL", "1") != "0" and self.ndata <= _PARALLEL_MAX_N
@@ -74,7 +77,12 @@ class log_likelihood(object):
 
     def _device_spec(self, kernel):
         """``kernel_to_spec``'s description, or else a sum's (``kernels.device_spec``) -- except on the multi-GPU route, where
-        sums keep the dense route; NotImplementedError for every other tree"""
+        sums keep the dense route; NotImplementedError for every other tree.  3-D coordinates: ``kernel_to_spec3``'s description
+        (the dense route under the multi-GPU engine, which has no 3-D K build, and for sums)"""
+        if self.three_d:
+            if self.distributed:
+                raise NotImplementedError("3-D coordinates keep the dense route under the multi-GPU engine")
+            return _kernels.device_spec(kernel, ndim=3)
         return _kernels.device_spec(kernel, allow_sum=not self.distributed, single=kernel_to_spec)
 
     def log_likelihood(self, kernel, ctx=None, resident=None):
@@ -88,7 +96,7 @@ class log_likelihood(object):
                 spec = None                       # any other scikit-learn kernel tree: it evaluates itself on the host
             if spec is None:
                 _, log_det, chi2, _ = ops.gp_solve_dense(kernel(self.X), self.y, self.y_err, want_alpha=False, ctx=ctx)
-            elif resident is not None and not isinstance(spec, ops.KernelSumSpec):     # (no resident variant of the sum solve)
+            elif resident is not None and not isinstance(spec, (ops.KernelSumSpec, ops.KernelSpec3)):   # (no resident variant of the sum and 3-D solves)
                 log_det, chi2 = ops.gp_solve_resident(spec, resident, ctx=ctx)
             else:
                 _, log_det, chi2, _ = ops.gp_solve(spec, self.X, self.y, self.y_err, want_alpha=False, ctx=ctx)
@@ -114,7 +122,7 @@ class log_likelihood(object):
         batched = []
         for i, kernel in enumerate(kernels):
             spec = None
-            if not self.distributed and self.ndata <= ops.BATCH_NMAX:
+            if not self.distributed and self.ndata <= ops.BATCH_NMAX and not self.three_d:
                 try:
                     spec = self._device_spec(kernel)
                 except NotImplementedError:
@@ -197,7 +205,7 @@ class log_likelihood(object):
         template = kernel
         # X, y, y_err do not change during the fit: they go to the device once, every evaluation sends only theta
         resident = None
-        if os.environ.get("TGP_ML_RESIDENT", "1") != "0" and not self.distributed:
+        if os.environ.get("TGP_ML_RESIDENT", "1") != "0" and not self.distributed and not self.three_d:
             resident = ops.ResidentProblem(self.X, self.y, self.y_err)
 
         def cost(theta, ctx=None, work=None):
@@ -220,6 +228,8 @@ class log_likelihood(object):
         return fitted
 
     def _use_exact_gradient(self, template):
+        if self.three_d:                                  # the exact gradient is 2-D: finite differences, whatever was asked for
+            return False
         if self.gradient == "analytic-vk":                # the exact gradient for all four kinds (seam S2h), asked for explicitly
             try:
                 if isinstance(self._device_spec(template), ops.KernelSumSpec):

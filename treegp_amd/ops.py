@@ -11,7 +11,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from ._lib import TgpKernel, TgpKernelSum, check, f64, ptr, as_xy
+from ._lib import TgpKernel, TgpKernel3, TgpKernelSum, check, f64, ptr, as_xy, as_xyz
 
 
 class KernelSpec(object):
@@ -62,11 +62,42 @@ class KernelSumSpec(object):
         return "KernelSumSpec(%r)" % (self.terms,)
 
 
+class KernelSpec3(object):
+    """One parametrised kernel over (n, 3) coordinates (tgp_kernel3 of include/tgp.h): ``m`` is the upper triangle of the
+    symmetric invLam, row-wise (xx, xy, xz, yy, yz, zz); ``ell`` the length scale of the isotropic von Karman kind.
+    ``treegp_amd.kernels.kernel_to_spec3`` derives it from a scikit-learn kernel object.  ``kernel_matrix``, ``gp_solve``,
+    ``gp_predict``, ``gp_predict_grad`` (result (m, 3)), ``gp_predict_cov`` and ``gp_predict_var`` take it wherever they take a
+    ``KernelSpec`` and go to the ``3`` entries; coordinates must then be (n, 3).  These calls run on this process's GPU whatever
+    the multi-GPU settings."""
+    __slots__ = ("kind", "amp", "m", "ell")
+
+    def __init__(self, kind, amp=1.0, m=(1.0, 0.0, 0.0, 1.0, 0.0, 1.0), ell=1.0):
+        m = tuple(float(v) for v in np.ravel(m))
+        if len(m) != 6:
+            raise ValueError("KernelSpec3.m holds invLam xx, xy, xz, yy, yz, zz: 6 numbers, got %d" % len(m))
+        self.kind, self.amp, self.m, self.ell = int(kind), float(amp), m, float(ell)
+
+    def to_c(self):
+        return TgpKernel3(self.kind, 3, self.amp, (C.c_double * 6)(*self.m), self.ell)
+
+    def __repr__(self):
+        return "KernelSpec3(kind=%d, amp=%r, m=%r, ell=%r)" % (self.kind, self.amp, self.m, self.ell)
+
+
 def _entry(lib, name, spec):
-    """the library entry `name` for a KernelSpec, its `_sum` namesake (same arguments) for a KernelSumSpec"""
+    """the library entry `name` for a KernelSpec, its `_sum` namesake (same arguments) for a KernelSumSpec, its `3` namesake for a
+    KernelSpec3"""
     if isinstance(spec, KernelSumSpec):
         name += "_sum"
+    elif isinstance(spec, KernelSpec3):
+        name += "3"
     return getattr(lib, name), name
+
+
+def _coords(spec, X):
+    """the coordinates as the entry of `spec` takes them: (n, 3) for a KernelSpec3, ``as_xy``'s (n, 2) otherwise (so a 2-D spec
+    given three columns keeps raising ValueError)"""
+    return as_xyz(X) if isinstance(spec, KernelSpec3) else as_xy(X)
 
 
 class Factor(object):
@@ -104,13 +135,13 @@ def kernel_matrix(spec, X, Y=None, ctx=None):
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
     fn, name = _entry(lib, "tgp_kernel_matrix", spec)
-    X2 = as_xy(X)
+    X2 = _coords(spec, X)
     n = X2.shape[0]
     if Y is None:
         out = np.empty((n, n))
         rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), n, None, 0, ptr(out))
     else:
-        Y2 = as_xy(Y)
+        Y2 = _coords(spec, Y)
         m = Y2.shape[0]
         out = np.empty((n, m))
         rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(Y2), m, ptr(out))
@@ -136,13 +167,13 @@ def gp_solve(spec, X, y, y_err=None, keep=False, want_alpha=True, ctx=None):
     """(alpha, logdet, y.alpha, factor|None) for K = amp k(X) + diag(y_err^2).
     Raises numpy.linalg.LinAlgError when K is not positive definite, as scipy.linalg.cholesky
     does at treegp/gp_interp.py:181."""
-    eng = None if isinstance(spec, KernelSumSpec) else _dist_engine(len(X), ctx)
+    eng = None if isinstance(spec, (KernelSumSpec, KernelSpec3)) else _dist_engine(len(X), ctx)
     if eng is not None:
         return eng.gp_solve(spec, X, y, y_err, keep=keep, want_alpha=want_alpha)
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
     fn, name = _entry(lib, "tgp_gp_solve", spec)
-    X2 = as_xy(X)
+    X2 = _coords(spec, X)
     n = X2.shape[0]
     y = f64(y)
     e = None if y_err is None else f64(y_err)
@@ -619,12 +650,12 @@ def gp_solve_grad_resident_any(spec, problem, ctx=None):
 
 def gp_predict(spec, X, alpha, Xs, ctx=None):
     """ys = k(Xs, X) @ alpha without materialising the cross kernel (gp_interp.py:177,183)."""
-    eng = None if isinstance(spec, KernelSumSpec) else _dist_engine(len(X), ctx)
+    eng = None if isinstance(spec, (KernelSumSpec, KernelSpec3)) else _dist_engine(len(X), ctx)
     if eng is not None:
         return eng.gp_predict(spec, X, alpha, Xs)
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
-    X2, Xs2 = as_xy(X), as_xy(Xs)
+    X2, Xs2 = _coords(spec, X), _coords(spec, Xs)
     alpha = f64(alpha)
     ys = np.empty(Xs2.shape[0])
     fn, name = _entry(lib, "tgp_gp_predict", spec)
@@ -640,9 +671,9 @@ def gp_predict_grad(spec, X, alpha, Xs, ctx=None):
     settings: the sum is one pass over the pairs, as ``gp_predict``'s."""
     ctx = ctx or _lib.get_ctx()
     lib = _lib.load_library()
-    X2, Xs2 = as_xy(X), as_xy(Xs)
+    X2, Xs2 = _coords(spec, X), _coords(spec, Xs)
     alpha = f64(alpha)
-    gs = np.empty((Xs2.shape[0], 2))
+    gs = np.empty((Xs2.shape[0], Xs2.shape[1]))            # (m, 2); (m, 3) for a KernelSpec3
     fn, name = _entry(lib, "tgp_gp_predict_grad", spec)
     rc = fn(ctx, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(alpha), ptr(Xs2), Xs2.shape[0], ptr(gs))
     check(ctx, rc, name)
@@ -653,7 +684,7 @@ def gp_predict_cov(spec, factor, X, Xs, ctx=None):
     """Posterior covariance k(Xs,Xs) - HT K^-1 HT^T (gp_interp.py:184-192) from a kept factor."""
     ctx = ctx or factor._ctx
     lib = _lib.load_library()
-    X2, Xs2 = as_xy(X), as_xy(Xs)
+    X2, Xs2 = _coords(spec, X), _coords(spec, Xs)
     m = Xs2.shape[0]
     cov = np.empty((m, m))
     fn, name = _entry(lib, "tgp_gp_predict_cov", spec)
@@ -667,7 +698,7 @@ def gp_predict_var(spec, factor, X, Xs, ctx=None):
     covariance is never formed (tgp_gp_predict_var; the reference's callers take np.diag of gp_interp.py:184-192)."""
     ctx = ctx or factor._ctx
     lib = _lib.load_library()
-    X2, Xs2 = as_xy(X), as_xy(Xs)
+    X2, Xs2 = _coords(spec, X), _coords(spec, Xs)
     m = Xs2.shape[0]
     var = np.empty(m)
     fn, name = _entry(lib, "tgp_gp_predict_var", spec)

@@ -59,7 +59,7 @@ def prior_diag_max(kernel, X):
     """max over X of k(x, x): amp for the parametrised kernels (the sum of the amplitudes for a sum of them),
     max(kernel.diag(X)) for any other kernel tree"""
     try:
-        return _kernels.device_spec(kernel).amp
+        return _kernels.device_spec(kernel, ndim=np.shape(X)[1] if np.ndim(X) == 2 else 1).amp
     except NotImplementedError:
         return float(np.max(kernel.diag(X)))
 
@@ -91,7 +91,7 @@ def gaussian_random_field(kernel, X, n_samples=1, random_state=0, y_err=None, nu
     K = kernel(X) and jitter = nugget * max k(x, x).  What the reference does with np.random.multivariate_normal(0, K).
 
     :param kernel:       kernel string (``eval_kernel``) or scikit-learn kernel object.
-    :param X:            coordinates (n, 1 or 2), or (n,) for 1-D.
+    :param X:            coordinates (n, 1, 2 or 3), or (n,) for 1-D.
     :param n_samples:    number of realisations.
     :param random_state: seed of ``np.random.default_rng``; realisation v is L z with z the v-th row of
                          ``default_rng(random_state).standard_normal((n_samples, n))``.
@@ -113,7 +113,7 @@ def gaussian_random_field(kernel, X, n_samples=1, random_state=0, y_err=None, nu
     jitter = nugget * prior_diag_max(kernel, X)
     Z = normals(n_samples, n, random_state)
     try:
-        spec = _kernels.device_spec(kernel)
+        spec = _kernels.device_spec(kernel, ndim=X.shape[1])
     except NotImplementedError:
         spec = None
     if spec is None:
