@@ -242,9 +242,10 @@ __global__ __launch_bounds__(256) void syrk_small_kernel(double *Abase, int64_t 
 //   strip == 0 : all tiles tj <= ti < T, XCD-aware super-tile enumeration (tilemap)
 //   strip  > 0 : only the first `strip` tile columns (the columns the next panels live in), so
 //                that their factorisation can start before the rest of the update has finished
+//   diag_full  : diagonal tiles (ti == tj) as full tiles, as before they were cut to their lower blocks (TGP_DIAG_FULL=1)
 template <int NSEG>
 __global__ __launch_bounds__(256, 2) void syrk_dtv_kernel(double *Abase, int64_t Np, int ob, int T, int strip, const double *P0,
-                                                          const double *P1) {
+                                                          const double *P1, int diag_full) {
     int ti, tj;
     if (strip == 0) {
         tilemap(blockIdx.x, T, ti, tj);
@@ -259,6 +260,17 @@ __global__ __launch_bounds__(256, 2) void syrk_dtv_kernel(double *Abase, int64_t
     const int64_t I = (int64_t)TGP_PW * ob + (int64_t)TGP_TB * ti;
     double *C = Abase + panel_off(pj, Np) + (I - pj * TGP_PW) * TGP_PW + (tj & 1) * TGP_TB;
     const int64_t oa = (int64_t)ti * TGP_TB * TGP_PW, obb = (int64_t)tj * TGP_TB * TGP_PW;
+    if (ti == tj && !diag_full) {            // only the blocks at or below the diagonal (gemm_tile.h: gemm_tile_dtv_diag)
+        SegPtrs<NSEG> sp;
+        sp.a[0] = P0 + oa;
+        sp.b[0] = P0 + obb;
+        if constexpr (NSEG > 1) {
+            sp.a[1] = P1 + oa;
+            sp.b[1] = P1 + obb;
+        }
+        gemm_tile_dtv_diag<TGP_PW, NSEG, false>(sp, C);
+        return;
+    }
     gemm_tile_dtv<4, TGP_PW, NSEG>(P0 + oa, P0 + obb, C, NSEG > 1 ? P1 + oa : nullptr, NSEG > 1 ? P1 + obb : nullptr);
 }
 
@@ -424,7 +436,8 @@ __device__ __forceinline__ void head_done(const HeadSignal &h) {
 // 1361.0 ms at N = 65 536, profiles/r04_fused_bulk_ab.txt -- the rest tiles start in lockstep when the head ends, so the
 // panel chain's first kernel waits a whole tile time for a slot, where after a separate head launch it finds the chip empty.)
 template <int NSEG>
-__global__ __launch_bounds__(256, 2) void syrk_segs_kernel(double *Abase, int64_t Np, int ob, int T, int strip, SegPtrs<NSEG> P) {
+__global__ __launch_bounds__(256, 2) void syrk_segs_kernel(double *Abase, int64_t Np, int ob, int T, int strip, SegPtrs<NSEG> P,
+                                                           int diag_full) {
     int ti, tj;
     if (strip == 0) {
         tilemap(blockIdx.x, T, ti, tj);
@@ -444,6 +457,10 @@ __global__ __launch_bounds__(256, 2) void syrk_segs_kernel(double *Abase, int64_
     for (int s = 0; s < NSEG; ++s) {
         sp.a[s] = P.a[s] + oa;
         sp.b[s] = P.a[s] + obb;
+    }
+    if (ti == tj && !diag_full) {            // only the blocks at or below the diagonal (gemm_tile.h: gemm_tile_dtv_diag)
+        gemm_tile_dtv_diag<TGP_PW, NSEG, true>(sp, C);
+        return;
     }
     gemm_tile_dtv_segs<4, TGP_PW, NSEG>(sp, C);
 }
@@ -705,6 +722,13 @@ void factor_panel(hipStream_t st, double *Pk, int64_t mk, double *W0, int *d_inf
     }
 }
 
+// TGP_DIAG_FULL=1: the diagonal tiles of syrk_dtv_kernel / syrk_segs_kernel as full 128 x 128 tiles (as before they were cut to
+// the blocks at or below the diagonal; same bits there) -- for A/B runs and tests/test_gpu_diag_tiles.py.  Read once.
+inline int diag_full() {
+    static const int v = [] { const char *e = getenv("TGP_DIAG_FULL"); return e ? (atoi(e) != 0 ? 1 : 0) : 0; }();
+    return v;
+}
+
 inline int small_t() {          // steps with at most this many tile rows run on the latency tile (16-row slices)
     static const int v = [] { const char *e = getenv("TGP_SMALL_T"); return e ? atoi(e) : 8; }();
     return v;
@@ -732,7 +756,7 @@ void launch_syrk(hipStream_t st, double *d_A, int64_t Np, int ob, int T, int str
         return;
     }
     const unsigned gs = strip == 0 ? (unsigned)tilemap_grid(T) : (unsigned)((int64_t)T * strip);
-    syrk_dtv_kernel<NSEG><<<gs, 256, 0, st>>>(d_A, Np, ob, T, strip, P0, P1);
+    syrk_dtv_kernel<NSEG><<<gs, 256, 0, st>>>(d_A, Np, ob, T, strip, P0, P1, diag_full());
 }
 
 // The depth-512 bulk update after the pair (k, k+1) as the persistent grid that keeps compute units clear for the chain.
@@ -933,13 +957,13 @@ int launch_potrf(tgp_ctx *ctx, double *d_A, int64_t Np, double *d_W, bool defer_
             const unsigned gs = (unsigned)((int64_t)T * 2);
             if (j == 1) {
                 SegPtrs<1> P{{seg_rows(k0, ob)}, {nullptr}};
-                syrk_segs_kernel<1><<<gs, 256, 0, s>>>(d_A, Np, ob, T, 2, P);
+                syrk_segs_kernel<1><<<gs, 256, 0, s>>>(d_A, Np, ob, T, 2, P, diag_full());
             } else if (j == 2) {
                 SegPtrs<2> P{{seg_rows(k0, ob), seg_rows(k0 + 1, ob)}, {nullptr, nullptr}};
-                syrk_segs_kernel<2><<<gs, 256, 0, s>>>(d_A, Np, ob, T, 2, P);
+                syrk_segs_kernel<2><<<gs, 256, 0, s>>>(d_A, Np, ob, T, 2, P, diag_full());
             } else {
                 SegPtrs<3> P{{seg_rows(k0, ob), seg_rows(k0 + 1, ob), seg_rows(k0 + 2, ob)}, {nullptr, nullptr, nullptr}};
-                syrk_segs_kernel<3><<<gs, 256, 0, s>>>(d_A, Np, ob, T, 2, P);
+                syrk_segs_kernel<3><<<gs, 256, 0, s>>>(d_A, Np, ob, T, 2, P, diag_full());
             }
         };
         auto factor_group = [&](hipStream_t s, int k0) {
@@ -959,7 +983,7 @@ int launch_potrf(tgp_ctx *ctx, double *d_A, int64_t Np, double *d_W, bool defer_
             SegPtrs<4> P{{seg_rows(k0, ob), seg_rows(k0 + 1, ob), seg_rows(k0 + 2, ob), seg_rows(k0 + 3, ob)},
                          {nullptr, nullptr, nullptr, nullptr}};
             const unsigned gs = strip == 0 ? (unsigned)tilemap_grid(T) : (unsigned)((int64_t)T * strip);
-            syrk_segs_kernel<4><<<gs, 256, 0, st>>>(d_A, Np, ob, T, strip, P);
+            syrk_segs_kernel<4><<<gs, 256, 0, st>>>(d_A, Np, ob, T, strip, P, diag_full());
         };
         // Below `tail_tiles` rows of trailing matrix the deeper grouping no longer pays (its strips and the longer
         // serial chain cost more than the per-tile overhead it saves: crossover at N ~ 24k): the tail runs in pairs.
@@ -1216,9 +1240,9 @@ int tgp_debug_syrk_loop(tgp_ctx *ctx, double *d_A, int64_t Np, int reps, double 
     if (getenv("TGP_DEBUG_SEGS")) {           // the depth-1024 kernel on the same two panels twice
         SegPtrs<4> P{{P0, P1, P0, P1}, {nullptr, nullptr, nullptr, nullptr}};
         const unsigned gs = (unsigned)tilemap_grid(T2);
-        syrk_segs_kernel<4><<<gs, 256, 0, st>>>(d_A, Np, 2, T2, 0, P);
+        syrk_segs_kernel<4><<<gs, 256, 0, st>>>(d_A, Np, 2, T2, 0, P, diag_full());
         TGP_HIP(hipEventRecord(ctx->ev[0], st));
-        for (int r = 0; r < reps; ++r) syrk_segs_kernel<4><<<gs, 256, 0, st>>>(d_A, Np, 2, T2, 0, P);
+        for (int r = 0; r < reps; ++r) syrk_segs_kernel<4><<<gs, 256, 0, st>>>(d_A, Np, 2, T2, 0, P, diag_full());
         TGP_HIP(hipEventRecord(ctx->ev[1], st));
         TGP_HIP(hipStreamSynchronize(st));
         float ms2 = 0.f;

@@ -727,8 +727,49 @@ __device__ __forceinline__ void gemm_tile_dtv_segs(const SegPtrs<NSEG> &sp, doub
                 for (int n = 0; n < 8; ++n)
                     acc[m][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[m][h].y, bf[n].y, acc[m][n], 0, 0, 0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-        if (more) store_b(buf ^ 1);
+        if constexpr (MT == 2 && NW == 4) {
+            // The chunk's turnover, placed by hand (sched_group_barrier: the order of the groups below is the order of the
+            // instructions; everything else goes where the compiler likes).  Left to itself hipcc issues the next chunk's 8 global
+            // loads and 11 of the 16 fragment reads between the workgroup barrier and the first matrix instruction, which then
+            // waits for the first read behind all of them, and -- with the sched_barrier(0) of the other forms -- the 4 staging
+            // stores, their vmcnt waits and the lgkmcnt(0) of the barrier behind the last one: some hundreds of cycles per
+            // chunk (of 4096 of matrix instructions) in which this wave has nothing in the pipe.  Here:
+            //   4 fragment reads, then matrix instructions 0 .. 4 with the other 4 reads of h = 0 between them;
+            //   the 8 global loads one per matrix instruction (5 .. 12), the 8 reads of h = 1 likewise (13 .. 20);
+            //   the staging stores TURN_TAIL matrix instructions before the chunk's end: their data arrived long before (issued
+            //   2700 cycles earlier; the buffer has had no reader since the previous barrier), and they have completed when the
+            //   barrier's lgkmcnt(0) comes.
+            // Same matrix instructions on the same operands in the same order per accumulator: same bits.  No register, LDS byte
+            // or barrier added (246 VGPRs, 36 864 B).  Depth-1024 kernel back to back (tools/syrk_loop.py, TGP_DEBUG_SEGS, Np =
+            // 32 768, five alternating launches per build): 14.655 -> 14.436 ms, spread 0.06 (profiles/diag_tiles_ab.txt);
+            // TURN_TAIL = 8 and 16 are equal within that spread.
+            constexpr int TURN_TAIL = 16;
+            if (more) store_b(buf ^ 1);
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);                   // 0x100 LDS read, 0x008 matrix instruction,
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                   // 0x020 global load, 0x200 LDS write
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, 64 - 21 - TURN_TAIL, 0);
+            __builtin_amdgcn_sched_group_barrier(0x200, 4, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, TURN_TAIL, 0);
+            __builtin_amdgcn_sched_barrier(0);          // nothing of the chunk moves behind the workgroup barrier
+        } else {
+            __builtin_amdgcn_sched_barrier(0);          // staging stores (they wait for the loads) behind the MFMAs
+            if (more) store_b(buf ^ 1);
+        }
         __syncthreads();
     };
 #pragma unroll
@@ -748,4 +789,173 @@ __device__ __forceinline__ void gemm_tile_dtv_segs(const SegPtrs<NSEG> &sp, doub
         for (int n = 0; n < 8; ++n)
 #pragma unroll
             for (int r = 0; r < 4; ++r) buf_st1_stream(-acc[m][n][r], rc, vc, ((m * 16 + 4 * r) * LD + n * 16) * 8);
+}
+
+
+// ---- the DTV tile on the diagonal (ti == tj): only the 16 x 16 blocks at or below the diagonal -----------------------------
+// A diagonal tile of the trailing matrix is symmetric and only its lower triangle is ever read (potrf128_body loads the ten lower
+// 32 x 32 blocks and masks the diagonal ones).  The eight 16-row m-tiles of the tile need 1, 2, ... 8 column blocks; with the
+// row assignment of the full tile (wave w: rows 32 w .. 32 w + 31) wave 3 would still need all eight and the workgroup ends with
+// its slowest wave.  Dealt as m-tiles w and 7 - w every wave has (w + 1) + (8 - w) = 9 blocks instead of 16.
+// Same staging of B (all 128 rows: m-tile 7 needs them), same chunk pipeline, same k order per element as the full tile: every
+// element at or below the diagonal gets the same bits; the 28 blocks above it are neither read nor written.
+constexpr int diag_deal_mtile(int w, int half) { return half == 0 ? w : 7 - w; }
+constexpr int diag_deal_nblocks(int w) { return (diag_deal_mtile(w, 0) + 1) + (diag_deal_mtile(w, 1) + 1); }
+// bit 8 i + j of the result: block (m-tile i, column block j) is computed by some wave; ~0 when two waves claim the same block
+constexpr unsigned long long diag_deal_cover() {
+    unsigned long long mask = 0;
+    for (int w = 0; w < 4; ++w)
+        for (int half = 0; half < 2; ++half) {
+            const int i = diag_deal_mtile(w, half);
+            for (int j = 0; j <= i; ++j) {
+                const unsigned long long bit = 1ull << (8 * i + j);
+                if (mask & bit) return ~0ull;
+                mask |= bit;
+            }
+        }
+    return mask;
+}
+constexpr unsigned long long diag_lower_blocks() {
+    unsigned long long mask = 0;
+    for (int i = 0; i < 8; ++i)
+        for (int j = 0; j <= i; ++j) mask |= 1ull << (8 * i + j);
+    return mask;
+}
+static_assert(diag_deal_nblocks(0) == 9 && diag_deal_nblocks(1) == 9 && diag_deal_nblocks(2) == 9 && diag_deal_nblocks(3) == 9,
+              "every wave of a diagonal tile computes nine blocks");
+static_assert(diag_deal_cover() == diag_lower_blocks(), "the deal covers exactly the blocks j <= i, each once");
+
+// one wave's share: W is the wave index (compile-time, so that the accumulators are), STREAM the C accesses of gemm_tile_dtv_segs
+template <int W, int KDEPTH, int NSEG, bool STREAM>
+__device__ __forceinline__ void dtv_diag_wave(const SegPtrs<NSEG> &sp, double *c_ptr) {
+    constexpr int LD = TGP_PW;
+    constexpr int LSB = DTV_LSB;
+    constexpr int BPT = 4, BROWS = 32;
+    constexpr int M0 = diag_deal_mtile(W, 0), M1 = diag_deal_mtile(W, 1);      // the two m-tiles
+    constexpr int N0 = M0 + 1, N1 = M1 + 1;                                    // their column blocks 0 .. N - 1 (N0 <= N1)
+    static_assert(N0 <= N1 && N0 + N1 == 9, "m-tile w and its mirror");
+    double (*ldsB)[128 * LSB] = reinterpret_cast<double (*)[128 * LSB]>(dtv_lds_storage());
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int l15 = lane & 15, l4 = lane >> 4;
+
+    __amdgpu_buffer_rsrc_t ra[NSEG], rb[NSEG];
+#pragma unroll
+    for (int s = 0; s < NSEG; ++s) {
+        ra[s] = tile_rsrc(sp.a[s], 128 * LD * 8);
+        rb[s] = tile_rsrc(sp.b[s], 128 * LD * 8);
+    }
+    const __amdgpu_buffer_rsrc_t rc = tile_rsrc(c_ptr, 128 * LD * 8);
+    const int va = (l15 * LD + 2 * l4) * 8;                     // A: row l15 of an m-tile, k-pair kq
+    const int srow = tid >> 3, kp = (tid & 7) * 2;
+    const int vb = (srow * LD + kp) * 8;
+    const int vc = (l4 * LD + l15) * 8;                         // C fragment of an m-tile: col = lane & 15, row = (lane >> 4) + 4r
+    const int fb = l15 * LSB + 2 * l4;
+
+    double2 areg[2][2][2];                                      // [set][m-tile][h]
+    double2 rbst[BPT];
+    auto load_a = [&](double2 (&dst)[2][2], __amdgpu_buffer_rsrc_t src, int k0) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            dst[0][h] = buf_ld2(src, va, (M0 * 16 * LD + k0 + 8 * h) * 8);
+            dst[1][h] = buf_ld2(src, va, (M1 * 16 * LD + k0 + 8 * h) * 8);
+        }
+    };
+    auto load_b = [&](__amdgpu_buffer_rsrc_t src, int k0) {
+#pragma unroll
+        for (int s = 0; s < BPT; ++s) rbst[s] = buf_ld2(src, vb, (s * BROWS * LD + k0) * 8);
+    };
+    auto store_b = [&](int buf) {
+#pragma unroll
+        for (int s = 0; s < BPT; ++s) *reinterpret_cast<double2 *>(&ldsB[buf][(srow + BROWS * s) * LSB + kp]) = rbst[s];
+    };
+    auto ld_c = [&](int soff) { return STREAM ? buf_ld1_stream(rc, vc, soff) : buf_ld1(rc, vc, soff); };
+    auto st_c = [&](double x, int soff) {
+        if constexpr (STREAM) buf_st1_stream(x, rc, vc, soff);
+        else buf_st1(x, rc, vc, soff);
+    };
+    load_a(areg[0], ra[0], 0);
+    load_b(rb[0], 0);
+
+    d4 acc0[N0], acc1[N1];
+#pragma unroll
+    for (int n = 0; n < N0; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc0[n][r] = ld_c(((M0 * 16 + 4 * r) * LD + n * 16) * 8);
+#pragma unroll
+    for (int n = 0; n < N1; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc1[n][r] = ld_c(((M1 * 16 + 4 * r) * LD + n * 16) * 8);
+    store_b(0);
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N0; ++n) acc0[n] = -acc0[n];
+#pragma unroll
+    for (int n = 0; n < N1; ++n) acc1[n] = -acc1[n];
+
+    constexpr int cps = KDEPTH / KB;
+    static_assert(cps % 2 == 0, "chunks are processed in register-set pairs");
+    auto step = [&](const int cc, const bool last_seg, __amdgpu_buffer_rsrc_t sa, __amdgpu_buffer_rsrc_t sb,
+                    __amdgpu_buffer_rsrc_t na, __amdgpu_buffer_rsrc_t nb, double2 (&cur)[2][2], double2 (&nxt)[2][2]) {
+        const int buf = cc & 1;
+        const bool wrap = (cc + 1 == cps);                       // wave-uniform
+        const bool more = !(wrap && last_seg);
+        if (more) {
+            const int k0 = wrap ? 0 : (cc + 1) * KB;
+            load_a(nxt, wrap ? na : sa, k0);
+            load_b(wrap ? nb : sb, k0);
+        }
+        const double *Bs = ldsB[buf];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            double2 bf[N1];
+#pragma unroll
+            for (int n = 0; n < N1; ++n) bf[n] = *reinterpret_cast<const double2 *>(&Bs[fb + n * 16 * LSB + 8 * h]);
+#pragma unroll
+            for (int n = 0; n < N0; ++n) acc0[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0][h].x, bf[n].x, acc0[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < N1; ++n) acc1[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[1][h].x, bf[n].x, acc1[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < N0; ++n) acc0[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[0][h].y, bf[n].y, acc0[n], 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < N1; ++n) acc1[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[1][h].y, bf[n].y, acc1[n], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);          // staging stores (they wait for the loads) behind the MFMAs
+        if (more) store_b(buf ^ 1);
+        __syncthreads();
+    };
+#pragma unroll
+    for (int s = 0; s < NSEG; ++s) {
+        const bool last = (s == NSEG - 1);
+        const __amdgpu_buffer_rsrc_t na = ra[last ? s : s + 1], nb = rb[last ? s : s + 1];
+#pragma unroll 1
+        for (int cc = 0; cc < cps; cc += 2) {
+            step(cc, last, ra[s], rb[s], na, nb, areg[0], areg[1]);
+            step(cc + 1, last, ra[s], rb[s], na, nb, areg[1], areg[0]);
+        }
+    }
+
+#pragma unroll
+    for (int n = 0; n < N0; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st_c(-acc0[n][r], ((M0 * 16 + 4 * r) * LD + n * 16) * 8);
+#pragma unroll
+    for (int n = 0; n < N1; ++n)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st_c(-acc1[n][r], ((M1 * 16 + 4 * r) * LD + n * 16) * 8);
+}
+
+// The diagonal tile of a 4-wave workgroup: C (128 x 128, lower 16 x 16 blocks only) -= sum over NSEG operand pairs of A B^T, where
+// A and B are the same 128 rows (sp.a[s] == sp.b[s] in effect; both are taken as given).  The four waves run their own unrolled
+// bodies (accumulators are compile-time indexed) and meet at the same number of workgroup barriers.
+template <int KDEPTH, int NSEG, bool STREAM>
+__device__ __forceinline__ void gemm_tile_dtv_diag(const SegPtrs<NSEG> &sp, double *c_ptr) {
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    switch (w) {                                               // wave-uniform
+        case 0: dtv_diag_wave<0, KDEPTH, NSEG, STREAM>(sp, c_ptr); break;
+        case 1: dtv_diag_wave<1, KDEPTH, NSEG, STREAM>(sp, c_ptr); break;
+        case 2: dtv_diag_wave<2, KDEPTH, NSEG, STREAM>(sp, c_ptr); break;
+        default: dtv_diag_wave<3, KDEPTH, NSEG, STREAM>(sp, c_ptr); break;
+    }
 }
