@@ -10,6 +10,7 @@
  *   S2f many small S2 + S2d at once     treegp/log_likelihood.py:43-62 for the problems of S2e (one evaluation of many fits)
  *   S2g many small S2 + diag(K^-1)      not in the reference: leave-one-out for the problems of S2e (R&W 5.4.2)
  *   S1s / S2s  S1, S2, S3 .. S3c for sums of kernels   treegp/kernels.py:17-59 (eval_kernel evals any tree)
+ *   S2j Fisher information of the hyper-parameters   not in the reference: error bars on a fitted kernel, from a kept factor
  *   S3  HT @ alpha                       treegp/gp_interp.py:177,183
  *   S3b posterior covariance             treegp/gp_interp.py:184-192
  *   S3c posterior variance               treegp/gp_interp.py:184-192, as the reference's tests use it: np.diag(y_cov)
@@ -355,6 +356,35 @@ int tgp_gp_predict_var_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k,
                            const double *Xs, int64_t m, double *var);
 int tgp_gp_loglik_grad_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
                            const double *alpha, double *grad /* nterms x 4 */);
+
+/* ---- S2j: Fisher information of the hyper-parameters from a kept factor -------------------------------------------------------
+ * Not in the reference, whose fits return a point estimate.  For the Gaussian likelihood
+ *   F_ij = 1/2 tr(C dK/dp_i C dK/dp_j),   C = (K + diag(yerr^2))^-1,
+ * and F^-1 is the covariance of the maximum-likelihood estimate; F does not depend on y.  The parameters are the device's own,
+ * as in S2d / S2h: p_t = (log amp_t, a_t, b_t, c_t) for term t (TGP_VK: a = c = 1 / ell^2, b = 0), P = 4 nterms of them in term
+ * order; the chain rule to theta stays on the host (kernels.fisher_theta: J F J^T with the Jacobians of the gradient).  With
+ * g = amp exp(-q / 2) for the Gaussian kinds and g = amp w(u) for the von Karman kinds (q, u, f, w as in S2h) the derivative
+ * matrices of a term are
+ *   D_0 = amp f(u)  (the kernel values without noise, diagonal exactly amp),  D_1 = -1/2 g dx^2,  D_2 = -g dx dy,  D_3 = -1/2 g dy^2,
+ * D_1 .. D_3 exactly zero on the diagonal, at an off-diagonal pair with u == 0 (where f = 1) and beyond the von Karman cutoff:
+ * the pair arithmetic of S2h, value for value.  With L the kept factor, S_r = L^-1 D_r L^-T and F[r][s] = 1/2 <S_r, S_s>.
+ * On the device: the D_r of a term in one launch (f and w once per pair), then per matrix the block substitution of S3b
+ * (Y = D L^-T, both its 128-block and its big-step form, unchanged), a transpose in the panel layout (D is symmetric, so
+ * Y^T = L^-1 D) and the substitution again; the sums over i, j < n as per-workgroup partial sums added by one workgroup in a
+ * fixed order, no atomics.  About 8 nterms n^3 flops, 24 nterms factorisations' worth.
+ * f: a factor kept by tgp_gp_solve / tgp_gp_solve_sum for the same X, kernel and yerr; it is only read (its inverse slabs are
+ * built on first use, as for S3b).  fisher: P x P doubles, row-major.
+ * Memory: P + 1 arrays of padded_n(n)^2 doubles plus the substitution's staging, in the context's scratch arenas.  If that
+ * exceeds the free device memory the call returns -2 with a message naming the entry and the bytes needed, before anything
+ * runs; there is no chunked form.  n != f->n, a NULL pointer, an unknown kind or nterms outside 1 .. TGP_SUM_MAX returns -1 with
+ * a message naming the entry and the field, before any device work.  Timings: [3] device compute.
+ * Promises: the same call gives the same bits, whatever the context did before; F[r][s] and F[s][r] carry the same bits; with
+ * nterms == 1 tgp_gp_fisher_sum IS tgp_gp_fisher, the same launches and the same bits; the factor serves every other entry
+ * afterwards exactly as before (tgp_gp_predict_var on it gives the same bits before and after).                             */
+int tgp_gp_fisher(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n,
+                  double *fisher /* 4 x 4 */);
+int tgp_gp_fisher_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n,
+                      double *fisher /* (4 nterms) x (4 nterms), row-major */);
 
 /* ---- S2i: the batched routes (S2e, S2f / S2h, S2g, S3f) for sums of kernels ---------------------------------------------------
  * The reference's regime is many small GPs, and its most physical kernel is a sum (an atmospheric term plus a long-range optical

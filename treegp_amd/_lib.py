@@ -108,6 +108,9 @@ SIGNATURES = {
     "tgp_gp_predict_cov_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
     "tgp_gp_predict_var_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _i64, _vp]),
     "tgp_gp_loglik_grad_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp]),
+    # seam S2j: Fisher information of the hyper-parameters from a kept factor
+    "tgp_gp_fisher": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp]),
+    "tgp_gp_fisher_sum": (C.c_int, [_vp, _vp, C.POINTER(TgpKernelSum), _vp, _i64, _vp]),
     # seam S2i: the batched entries for sums, each its namesake's prototype with an array of tgp_kernel_sum
     "tgp_gp_solve_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_gp_posterior_batch_sum": (C.c_int, [_vp, C.c_int, C.POINTER(TgpKernelSum), _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.c_int,

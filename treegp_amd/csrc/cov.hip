@@ -907,3 +907,289 @@ extern "C" int tgp_gp_loglik_grad_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_ker
     ctx->timings[3] = ms;
     return 0;
 }
+
+// ---- Fisher information of the hyper-parameters from a kept factor (seam S2j) ------------------------------------------------------
+//   F[r][s] = 1/2 tr(C D_r C D_s) = 1/2 <S_r, S_s>,   C = (K + diag(yerr^2))^-1 = L^-T L^-1,   S_r = L^-1 D_r L^-T
+// for the P = 4 T derivative matrices D_r = dK / d(log amp_t, a_t, b_t, c_t) of the T terms, in term order: the pair arithmetic of
+// loglik_grad_block (post_tile.h) stored instead of summed.  The inverse of F is the covariance of the maximum-likelihood
+// estimate; F does not depend on y.  Five steps, every array Np x Np in the 256-column panel layout of Bt:
+//   1  fisher_dpanels_kernel   D_0 .. D_3 of one term, f and w evaluated once per pair, rows and columns >= n zero
+//   2  cov_substitute          Y = D L^-T                        (the launches of the covariance, unchanged)
+//   3  fisher_transpose_kernel Y^T = L^-1 D                      (D is symmetric), through LDS tiles
+//   4  cov_substitute          S = Y^T L^-T
+//   5  fisher_pairs_kernel     partial sums of S_r[i,j] S_s[i,j], i, j < n, per workgroup, for every pair of terms;
+//      fisher_reduce_kernel    one workgroup per pair of terms adds them in a fixed order.  No atomics.
+// P + 1 arrays: D_r is written to slot r + 1; Y_r is transposed into slot r, which the matrix before it has left, so S_r ends
+// in slot r.  The factor is only read (its inverse slabs are built on first use, as for the covariance).
+namespace {
+#define TGP_FISHER_ROWS 32      // rows of a panel per workgroup of the derivative panels
+template <int KE>
+__device__ __forceinline__ void fisher_pair(const KParams &p, double xi, double yi, double xj, double yj, bool diag, bool in,
+                                            const double *tab_f, const double *tab_w, double v[4]) {
+    v[0] = v[1] = v[2] = v[3] = 0.0;
+    if (!in) return;
+    if (diag) { v[0] = p.amp; return; }                                  // d K_ii / d log amp = amp exactly, no slope
+    const double dx = xi - xj, dy = yi - yj;
+    double g;
+    if constexpr (KE == KE_GAUSS) {
+        g = p.amp * exp(-0.5 * quad_form(p, dx, dy));
+        v[0] = g;
+    } else {
+        const double u = (KE == KE_VK) ? sqrt(dx * dx + dy * dy) * p.inv_ell : sqrt(quad_form(p, dx, dy));
+        if (u == 0.0) { v[0] = p.amp; return; }                          // coincident points: f = 1, no slope
+        v[0] = p.amp * vonkarman_unit_tab(u, tab_f);
+        g = p.amp * vonkarman_slope_tab(u, tab_w);                       // exactly 0 beyond the value's cutoff
+    }
+    v[1] = -0.5 * g * dx * dx;
+    v[2] = -g * dx * dy;
+    v[3] = -0.5 * g * dy * dy;
+}
+
+// TGP_FISHER_ROWS rows x one 256-column panel per workgroup; a thread owns two neighbouring columns (one 16-byte store per
+// array and row, 2 KiB contiguous per half workgroup), the two halves of the workgroup take alternate rows
+template <int KE>
+__global__ __launch_bounds__(256) void fisher_dpanels_kernel(KParams p, const double *__restrict__ X, int64_t n, int64_t Np,
+                                                             double *__restrict__ D0, double *__restrict__ D1,
+                                                             double *__restrict__ D2, double *__restrict__ D3) {
+    __shared__ double tab_f[KE == KE_GAUSS ? 1 : 6 * K56_NDEG], tab_w[KE == KE_GAUSS ? 1 : 6 * K16_NDEG];
+    if constexpr (KE != KE_GAUSS) {
+        vonkarman_stage_table(tab_f);
+        vonkarman_slope_stage_table(tab_w);
+        __syncthreads();
+    }
+    const int tid = threadIdx.x;
+    const int64_t j0 = (int64_t)blockIdx.x * TGP_PW + 2 * (tid & 127);
+    const int64_t i0 = (int64_t)blockIdx.y * TGP_FISHER_ROWS + (tid >> 7);
+    const bool in0 = j0 < n, in1 = j0 + 1 < n;
+    const double xj0 = in0 ? X[2 * j0] : 0.0, yj0 = in0 ? X[2 * j0 + 1] : 0.0;
+    const double xj1 = in1 ? X[2 * j0 + 2] : 0.0, yj1 = in1 ? X[2 * j0 + 3] : 0.0;
+    for (int r = 0; r < TGP_FISHER_ROWS; r += 2) {
+        const int64_t i = i0 + r;                                        // < Np: the grid covers Np / TGP_FISHER_ROWS row blocks
+        const bool ini = i < n;
+        const double xi = ini ? X[2 * i] : 0.0, yi = ini ? X[2 * i + 1] : 0.0;
+        double v0[4], v1[4];
+        fisher_pair<KE>(p, xi, yi, xj0, yj0, i == j0, ini && in0, tab_f, tab_w, v0);
+        fisher_pair<KE>(p, xi, yi, xj1, yj1, i == j0 + 1, ini && in1, tab_f, tab_w, v1);
+        const int64_t e = panel_elem(i, j0, Np);
+        *(double2 *)(D0 + e) = make_double2(v0[0], v1[0]);
+        *(double2 *)(D1 + e) = make_double2(v0[1], v1[1]);
+        *(double2 *)(D2 + e) = make_double2(v0[2], v1[2]);
+        *(double2 *)(D3 + e) = make_double2(v0[3], v1[3]);
+    }
+}
+
+// out = in^T for Np x Np arrays in the panel layout: one 64 x 64 tile per workgroup through LDS (rows padded to 65 doubles), 16-byte
+// loads and stores, 512 B contiguous per tile row on both sides
+__global__ __launch_bounds__(256) void fisher_transpose_kernel(const double *__restrict__ in, double *__restrict__ out, int64_t Np) {
+    __shared__ double tile[64][65];
+    const int tid = threadIdx.x;
+    const int c = 2 * (tid & 31), r0 = tid >> 5;
+    const int64_t ti = blockIdx.y, tj = blockIdx.x;                      // the tile's rows ti * 64 .., columns tj * 64 .. of `in`
+#pragma unroll
+    for (int r = r0; r < 64; r += 8) {
+        const double2 v = *(const double2 *)(in + panel_elem(ti * 64 + r, tj * 64 + c, Np));
+        tile[r][c] = v.x;
+        tile[r][c + 1] = v.y;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = r0; r < 64; r += 8)                                     // row tj * 64 + r of `out`, columns ti * 64 + c, + 1
+        *(double2 *)(out + panel_elem(tj * 64 + r, ti * 64 + c, Np)) = make_double2(tile[c][r], tile[c + 1][r]);
+}
+
+// Term pair q = blockIdx.z -> (tr >= ts): the 16 sums of S_{4 tr + r}[i,j] S_{4 ts + s}[i,j] over rows i0 .. i0 + 63 of panel
+// blockIdx.x, i, j < n, to partial[((q * nrb + blockIdx.y) * nP + blockIdx.x) * 16 + 4 r + s].  A lane adds its products in row
+// order, then the xor tree across the wave and the four waves in order.  `slot`: doubles between two arrays.
+__global__ __launch_bounds__(256) void fisher_pairs_kernel(const double *__restrict__ S, int64_t slot, int64_t Np, int64_t n,
+                                                           double *__restrict__ partial) {
+    __shared__ double red[4][16];
+    const int tid = threadIdx.x;
+    int64_t tr, ts;
+    tri_index(blockIdx.z, tr, ts);
+    const double *A = S + 4 * tr * slot, *B = S + 4 * ts * slot;
+    const int64_t j0 = (int64_t)blockIdx.x * TGP_PW + 2 * (tid & 127);
+    const int64_t i0 = (int64_t)blockIdx.y * 64 + (tid >> 7);
+    double acc[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) acc[q] = 0.0;
+    if (j0 < n) {
+        const bool in1 = j0 + 1 < n;
+        for (int r = 0; r < 64; r += 2) {
+            const int64_t i = i0 + r;
+            if (i >= n) break;
+            const int64_t e = panel_elem(i, j0, Np);
+            double2 a[4], b[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                a[q] = *(const double2 *)(A + q * slot + e);
+                b[q] = *(const double2 *)(B + q * slot + e);
+                if (!in1) a[q].y = 0.0;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc[4 * q + s] = fma(a[q].y, b[s].y, fma(a[q].x, b[s].x, acc[4 * q + s]));
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        double v = acc[q];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if ((tid & 63) == 0) red[tid >> 6][q] = v;
+    }
+    __syncthreads();
+    if (tid < 16)
+        partial[(((int64_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 16 + tid] =
+            (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+}
+
+// fixed-order sum of the `count` partial sums of term pair blockIdx.x (one workgroup each: the result does not depend on the
+// schedule), the 16 sums to out[blockIdx.x * 16 ..]
+__global__ __launch_bounds__(256) void fisher_reduce_kernel(const double *__restrict__ partial, int64_t count, double *__restrict__ out) {
+    __shared__ double red[256][17];
+    const int tid = threadIdx.x;
+    const double *part = partial + (int64_t)blockIdx.x * count * 16;
+    double acc[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) acc[s] = 0.0;
+    for (int64_t q = tid; q < count; q += 256)
+#pragma unroll
+        for (int s = 0; s < 16; ++s) acc[s] += part[q * 16 + s];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) red[tid][s] = acc[s];
+    __syncthreads();
+    for (int step = 128; step > 0; step >>= 1) {
+        if (tid < step)
+            for (int s = 0; s < 16; ++s) red[tid][s] += red[tid + step][s];
+        __syncthreads();
+    }
+    if (tid < 16) out[(int64_t)blockIdx.x * 16 + tid] = red[0][tid];
+}
+
+// the checked arguments of both entries: -1 with a message naming `fn` and the field, before any device work
+int fisher_check(tgp_ctx *ctx, const tgp_factor *f, const tgp_kernel *terms, int nterms, const double *X, int64_t n,
+                 const double *fisher, const char *fn) {
+    const std::string who = std::string(fn) + ": ";
+    if (!f) { ctx->err = who + "f must not be NULL"; return -1; }
+    if (!terms) { ctx->err = who + "k must not be NULL"; return -1; }
+    if (!X) { ctx->err = who + "X must not be NULL"; return -1; }
+    if (!fisher) { ctx->err = who + "fisher must not be NULL"; return -1; }
+    if (n != f->n || n < 1) {
+        ctx->err = who + "n = " + std::to_string((long long)n) + " is not the factor's n = " + std::to_string((long long)f->n);
+        return -1;
+    }
+    for (int t = 0; t < nterms; ++t)
+        if (kind_to_ke(terms[t].kind) < 0) {
+            ctx->err = who + "unknown kernel kind " + std::to_string(terms[t].kind) + " in term " + std::to_string(t);
+            return -1;
+        }
+    return 0;
+}
+
+int fisher_run(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *terms, int T, const double *X, int64_t n, double *fisher,
+               const char *fn) {
+    TGP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t Np = f->Np, nP = Np / TGP_PW;
+    const int P = 4 * T, npairs = T * (T + 1) / 2;
+    const int64_t nrb = (n + 63) / 64, nparts = nrb * nP;
+    const int64_t slot = Np * Np;                                        // doubles per array
+    TGP_ARG(Np <= 65535 && Np % TGP_PW == 0);
+    // memory, before anything runs: the arena (coordinates, P + 1 arrays, partial sums and results) in `scratch`, the
+    // substitution's staging in `scratch2` and, where the big-step substitution has to build them, the factor's inverse slabs
+    const size_t arena = rup((size_t)2 * n * 8) + (size_t)(P + 1) * rup((size_t)slot * 8) + rup((size_t)npairs * nparts * 16 * 8) +
+                         rup((size_t)npairs * 16 * 8);
+    int step = 0;
+    const bool no_big = getenv("TGP_COV_BIG") && atoi(getenv("TGP_COV_BIG")) == 0;
+    const bool big = !no_big && potrs_big_step(Np, &step);
+    const size_t staging = big ? (size_t)Np * 1024 * 8 : 0;
+    const size_t slabs = (big && !f->d_slabs2 && !(f->d_slabs && f->slab_S == 1024))
+                             ? vslab_bytes(Np, 1024) + (ctx->vslab_tt_bytes < (size_t)Np * 1024 * 8 ? (size_t)Np * 1024 * 8 : 0) : 0;
+    size_t fr = 0, tot = 0;
+    TGP_HIP(hipMemGetInfo(&fr, &tot));
+    const double need = (double)arena + (double)staging + (double)slabs;
+    const double avail = (double)fr + (double)ctx->scratch_bytes + (double)ctx->scratch2_bytes;
+    if (need > avail) {
+        ctx->err = std::string(fn) + ": needs " + std::to_string((unsigned long long)need) + " bytes of device memory (" +
+                   std::to_string(P + 1) + " arrays of Np^2 = " + std::to_string((long long)Np) + "^2 doubles and the substitution's " +
+                   "staging), " + std::to_string((unsigned long long)avail) + " are free";
+        return -2;
+    }
+    int rc = tgp_ensure_scratch(ctx, arena);
+    if (rc) return rc;
+    char *base = (char *)ctx->scratch;
+    size_t off = 0;
+    auto take = [&](size_t b) { char *p = base + off; off += rup(b); return (double *)p; };
+    double *d_X = take((size_t)2 * n * 8);
+    double *d_S = take((size_t)slot * 8);                                // slot s at d_S + s * slotr
+    const int64_t slotr = (int64_t)(rup((size_t)slot * 8) / 8);          // (= slot: Np^2 * 8 is a multiple of 256)
+    off += (size_t)P * rup((size_t)slot * 8);
+    double *d_part = take((size_t)npairs * nparts * 16 * 8);
+    double *d_out = take((size_t)npairs * 16 * 8);
+    TGP_HIP(hipEventRecord(ctx->ev[0], st));
+    TGP_HIP(hipMemcpyAsync(d_X, X, (size_t)2 * n * 8, hipMemcpyHostToDevice, st));
+    const dim3 dgrid((unsigned)nP, (unsigned)(Np / TGP_FISHER_ROWS));
+    for (int t = 0; t < T; ++t) {
+        double *D = d_S + (int64_t)(4 * t + 1) * slotr;
+        const KParams p = make_kparams(&terms[t]);
+        switch (kind_to_ke(terms[t].kind)) {                             // fisher_check has seen the kinds
+            case KE_GAUSS: fisher_dpanels_kernel<KE_GAUSS><<<dgrid, 256, 0, st>>>(p, d_X, n, Np, D, D + slotr, D + 2 * slotr, D + 3 * slotr); break;
+            case KE_VK: fisher_dpanels_kernel<KE_VK><<<dgrid, 256, 0, st>>>(p, d_X, n, Np, D, D + slotr, D + 2 * slotr, D + 3 * slotr); break;
+            default: fisher_dpanels_kernel<KE_AVK><<<dgrid, 256, 0, st>>>(p, d_X, n, Np, D, D + slotr, D + 2 * slotr, D + 3 * slotr); break;
+        }
+    }
+    TGP_HIP(hipGetLastError());
+    CovPlan pl;
+    pl.n = n; pl.m = n; pl.Np = Np; pl.Mp = Np;
+    pl.nP = pl.nPm = (int)nP;
+    pl.d_X = pl.d_Xs = pl.d_C = pl.d_v = pl.d_kss = nullptr;
+    const dim3 tgrid((unsigned)(Np / 64), (unsigned)(Np / 64));
+    for (int r = 0; r < P; ++r) {
+        pl.d_Bt = d_S + (int64_t)(r + 1) * slotr;
+        rc = cov_substitute(ctx, f, pl, false);                          // Y = D L^-T
+        if (rc) return rc;
+        fisher_transpose_kernel<<<tgrid, 256, 0, st>>>(pl.d_Bt, d_S + (int64_t)r * slotr, Np);
+        pl.d_Bt = d_S + (int64_t)r * slotr;
+        rc = cov_substitute(ctx, f, pl, false);                          // S = Y^T L^-T
+        if (rc) return rc;
+    }
+    fisher_pairs_kernel<<<dim3((unsigned)nP, (unsigned)nrb, (unsigned)npairs), 256, 0, st>>>(d_S, slotr, Np, n, d_part);
+    fisher_reduce_kernel<<<(unsigned)npairs, 256, 0, st>>>(d_part, nparts, d_out);
+    TGP_HIP(hipGetLastError());
+    TGP_HIP(hipEventRecord(ctx->ev[1], st));
+    double sums[TGP_SUM_MAX * (TGP_SUM_MAX + 1) / 2 * 16];
+    TGP_HIP(hipMemcpyAsync(sums, d_out, (size_t)npairs * 16 * 8, hipMemcpyDeviceToHost, st));
+    TGP_HIP(hipStreamSynchronize(st));
+    // F = 1/2 T from the lower triangle, mirrored: F[r][s] and F[s][r] carry the same bits
+    for (int q = 0; q < npairs; ++q) {
+        int64_t tr, ts;
+        tri_index(q, tr, ts);
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                const int r = 4 * (int)tr + a, s = 4 * (int)ts + b;
+                if (s > r) continue;
+                const double v = 0.5 * sums[q * 16 + 4 * a + b];
+                fisher[(size_t)r * P + s] = v;
+                fisher[(size_t)s * P + r] = v;
+            }
+    }
+    float ms = 0.f;
+    TGP_HIP(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+    ctx->timings[3] = ms;                       // device compute
+    return 0;
+}
+}  // namespace
+
+extern "C" int tgp_gp_fisher(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X, int64_t n, double *fisher) {
+    if (!ctx) return -1;
+    if (fisher_check(ctx, f, k, 1, X, n, fisher, "tgp_gp_fisher")) return -1;
+    return fisher_run(ctx, f, k, 1, X, n, fisher, "tgp_gp_fisher");
+}
+
+extern "C" int tgp_gp_fisher_sum(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel_sum *k, const double *X, int64_t n, double *fisher) {
+    if (!ctx) return -1;
+    if (tgp_ksum_check(ctx, k, "tgp_gp_fisher_sum")) return -1;
+    if (k->nterms == 1) return tgp_gp_fisher(ctx, f, &k->term[0], X, n, fisher);
+    if (fisher_check(ctx, f, k->term, k->nterms, X, n, fisher, "tgp_gp_fisher_sum")) return -1;
+    return fisher_run(ctx, f, k->term, k->nterms, X, n, fisher, "tgp_gp_fisher_sum");
+}

@@ -358,6 +358,46 @@ class GPInterpolation(object):
             total = -np.inf
         return total if np.isfinite(total) else -np.inf
 
+    # -- error bars on the hyper-parameters (not in the reference) --------------------------------
+    def return_fisher_information(self, theta=None):
+        """F_theta (ntheta, ntheta), the Fisher information of the Gaussian likelihood for the current (or the given)
+        hyper-parameters: F_ij = 1/2 tr(C dK/dtheta_i C dK/dtheta_j), C = (K + diag(y_err^2))^-1 (white noise included); its
+        inverse is the covariance of the maximum-likelihood estimate (``return_theta_covariance``).  It does not depend on y.
+        Mirrors ``return_loo_log_predictive``: a temporary factor of its own (``ops.gp_fisher`` on it, include/tgp.h seam S2j;
+        about 24 factorisations' worth of flops per term), ``_alpha`` and the kept factor are left untouched.  Fixed
+        hyper-parameters have no row.  numpy.linalg.LinAlgError when K is not positive definite; NotImplementedError for 3-D
+        coordinates (the device has no 3-D derivative) and for kernel trees that take the dense route (WhiteKernel, Matern,
+        more than four terms), which has no derivative matrices."""
+        kernel = copy.deepcopy(self.kernel)
+        if theta is not None:
+            kernel = kernel.clone_with_theta(theta)
+        if _three_d(self._X):
+            raise NotImplementedError("return_fisher_information: 3-D coordinates have no derivative matrices on the device "
+                                      "(only the K build, predict and covariance take (n, 3) coordinates)")
+        try:
+            spec = self._device_spec(kernel)
+        except NotImplementedError as ex:
+            raise NotImplementedError("return_fisher_information needs a kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
+                                      "AnisotropicVonKarman or a sum of up to four of them); this one takes the dense route, which "
+                                      "has no derivative matrices: %s" % ex)
+        with self._scope():
+            factor = ops.gp_solve(spec, self._X, self._residual(), self._y_err, keep=True, want_alpha=False)[3]
+            try:
+                F_p = ops.gp_fisher(spec, factor, self._X)
+            finally:
+                factor.free(keep_memory=True)
+        return _kernels.fisher_theta(kernel, F_p)
+
+    def return_theta_covariance(self, theta=None):
+        """The inverse of ``return_fisher_information(theta)``: the covariance of the maximum-likelihood estimate of theta
+        (Cramer-Rao), e.g. ``np.sqrt(np.diag(gp.return_theta_covariance()))`` for the one-sigma errors after ``solve()``.
+        Through a Cholesky factorisation: numpy.linalg.LinAlgError when F_theta is not positive definite (a hyper-parameter the
+        data do not constrain).  Raises as ``return_fisher_information`` otherwise."""
+        F = self.return_fisher_information(theta)
+        L = np.linalg.cholesky(F)                           # LinAlgError: not positive definite
+        Li = np.linalg.solve(L, np.eye(len(L)))
+        return Li.T.dot(Li)
+
     # -- leave-group-out (not in the reference) --------------------------------------------------
     def _lgo_solve(self, kernel, perm, starts, want_cov):
         """lgo_quantities of the problem permuted by ``perm`` (the groups contiguous) from a temporary factor of its own:

@@ -354,6 +354,19 @@ def sum_spec_jacobian(kernel):
     return out
 
 
+def fisher_theta(kernel, F_p):
+    """J F_p J^T: the Fisher information of scikit-learn's theta from ``ops.gp_fisher``'s matrix in the device's parameters
+    (log amp_t, a_t, b_t, c_t per term).  J is ``spec_jacobian(kernel, von_karman=True)`` (ntheta x 4) for one parametrised
+    kernel and ``sum_spec_jacobian(kernel)`` for a sum; fixed hyper-parameters have no row in J and drop out.
+    NotImplementedError for the trees ``device_spec`` does not describe."""
+    device_spec(kernel)                                     # the same gate as the device route (raises NotImplementedError)
+    J = sum_spec_jacobian(kernel) if isinstance(kernel, Sum) else spec_jacobian(kernel, von_karman=True)
+    F_p = np.asarray(F_p, dtype=np.float64)
+    if F_p.shape != (J.shape[1], J.shape[1]):
+        raise ValueError("fisher_theta: F_p has shape %r, the kernel needs (%d, %d)" % (F_p.shape, J.shape[1], J.shape[1]))
+    return J.dot(F_p).dot(J.T)
+
+
 def spec_jacobian(kernel, *, von_karman=False):
     """d(log amp, a, b, c) / d theta, shape (ntheta, 4), for the Gaussian kernel trees ``kernel_to_spec`` accepts
     (theta in scikit-learn's order: a Product's k1 first).  ``ops.gp_loglik_grad`` returns d logL / d(log amp, a, b, c);

@@ -200,6 +200,28 @@ class log_likelihood(object):
             return -np.inf, np.zeros(ntheta)
         return ll, jac.dot(g4)
 
+    def fisher_information(self, kernel, ctx=None):
+        """F_theta (ntheta, ntheta): the Fisher information of the Gaussian likelihood at ``kernel``'s hyper-parameters,
+        F_ij = 1/2 tr(C dK/dtheta_i C dK/dtheta_j) with C = (K + diag(y_err^2))^-1; its inverse is the covariance of the
+        maximum-likelihood estimate.  It does not depend on y.  One solve that keeps its factor, ``ops.gp_fisher`` on it
+        (include/tgp.h, seam S2j) and ``kernels.fisher_theta`` on the host.  NotImplementedError for 3-D coordinates and for
+        kernel trees without a device form; numpy.linalg.LinAlgError when K is not positive definite."""
+        if self.three_d:
+            raise NotImplementedError("fisher_information: the device has no derivative matrices for 3-D coordinates")
+        try:
+            spec = _kernels.device_spec(kernel, single=kernel_to_spec)
+        except NotImplementedError as ex:
+            raise NotImplementedError("fisher_information needs a kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
+                                      "AnisotropicVonKarman or a sum of up to four of them); WhiteKernel, Matern and longer "
+                                      "sums take the dense route, which has no derivative matrices: %s" % ex)
+        # y plays no part in F: the solve is only what builds and keeps the factor
+        _, _, _, factor = ops.gp_solve(spec, self.X, self.y, self.y_err, keep=True, want_alpha=False, ctx=ctx)
+        try:
+            F_p = ops.gp_fisher(spec, factor, self.X, ctx=ctx)
+        finally:
+            factor.free(keep_memory=True)
+        return _kernels.fisher_theta(kernel, F_p)
+
     def optimizer(self, kernel):
         """L-BFGS-B on -log L over theta (log_likelihood.py:43-62)."""
         template = kernel

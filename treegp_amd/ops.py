@@ -749,6 +749,30 @@ def gp_loglik_grad_sum(sumspec, factor, X, alpha, ctx=None):
     return grad
 
 
+def gp_fisher(spec, factor, X, ctx=None):
+    """Fisher information of the Gaussian likelihood in the device's own parameters, (4 T, 4 T) for the T terms of ``spec`` (a
+    ``KernelSpec``: T = 1; a ``KernelSumSpec``): F[r][s] = 1/2 tr(C D_r C D_s) with C = (K + diag(y_err^2))^-1 and
+    D_{4 t + k} = dK / d(log amp_t, a_t, b_t, c_t)[k], from the factor of one ``gp_solve(spec, ..., keep=True)`` of the same X,
+    kernel and y_err (``tgp_gp_fisher`` / ``tgp_gp_fisher_sum``, seam S2j).  ``kernels.fisher_theta`` maps it to scikit-learn's
+    theta.  Bitwise symmetric; the factor is only read.  There is no 3-D derivative on the device: ValueError for a
+    ``KernelSpec3``, and for a factor that was freed.  Runs on this process's GPU whatever the multi-GPU settings."""
+    if isinstance(spec, KernelSpec3):
+        raise ValueError("gp_fisher: the device has no derivative matrices for 3-D coordinates (KernelSpec3)")
+    if not isinstance(spec, (KernelSpec, KernelSumSpec)):
+        raise ValueError("gp_fisher: spec must be a KernelSpec or a KernelSumSpec, got %r" % (type(spec).__name__,))
+    if factor is None or not getattr(factor, "_h", None):
+        raise ValueError("gp_fisher: the factor was freed (keep one with gp_solve(..., keep=True))")
+    ctx = ctx or factor._ctx
+    lib = _lib.load_library()
+    X2 = as_xy(X)
+    nterms = len(spec.terms) if isinstance(spec, KernelSumSpec) else 1
+    F = np.empty((4 * nterms, 4 * nterms))
+    fn, name = _entry(lib, "tgp_gp_fisher", spec)
+    rc = fn(ctx, factor._h, C.byref(spec.to_c()), ptr(X2), X2.shape[0], ptr(F))
+    check(ctx, rc, name)
+    return F
+
+
 # ---- pair binning across ranks (SURVEY 8e): i-tiles / bootstrap resamples dealt to the ranks ------
 _pair = threading.local()                  # per thread: the tests run virtual ranks as threads
 
