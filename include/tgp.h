@@ -17,6 +17,7 @@
  *   S3d realisations y = L z             np.random.multivariate_normal(0, K) at tests/treegp_test_helper.py:64-66, 95-97
  *   S3e diag(K^-1) of a kept factor      not in the reference: leave-one-out residuals and variances (R&W 5.4.2)
  *   S3g gradient of HT @ alpha           not in the reference: d/dX2 of treegp/gp_interp.py:177,183 (kernels.py:114-126, 249-276, 355-381)
+ *   S3l local kriging                    not in the reference: treegp/gp_interp.py:177-192 on each query's k nearest stars, no n x n factor
  *   S3f many small S3b / S3c at once    treegp/gp_interp.py:184-192 for the problems of S2e, README.rst:28
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
@@ -205,6 +206,40 @@ int tgp_gp_predict(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n
  * device time.                                                                                                             */
 int tgp_gp_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n,
                         const double *alpha, const double *Xs, int64_t m, double *gs);
+
+/* ---- S3l: local kriging -- every query conditioned on its kn nearest training points alone ----------------------------------------
+ * Not in the reference, whose predict is one dense factorisation of the whole K + diag(yerr^2) (treegp/gp_interp.py:177-192) and
+ * ends where that factor stops fitting on a GPU.  A prediction is determined, to all useful digits, by the stars within a few
+ * correlation lengths: here the cost is linear in m, there is no n x n anything, and with the 2-point-correlation optimisers
+ * (S4, any n, no factorisation) initialize -> solve -> predict_local is a complete pipeline for catalogues of 10^5 - 10^6 stars.
+ * Definition.  k: one tgp_kernel of any of the four kinds; kn in 1 .. 128, clipped to n.
+ *   metric       "nearest" = most correlated: Euclidean distance in u = R x, R^T R = invLam with R the upper-triangular 2 x 2
+ *                Cholesky factor computed on the host (TGP_ARBF, TGP_AVK), R = I for TGP_RBF / TGP_VK; u0 = r00 x + (r01 y), u1 =
+ *                r11 y, each product and sum rounded on its own; d2 = fl(fl(du0^2) + fl(du1^2)).
+ *   S(j)         the kn training rows with the smallest d2 to query j, ties to the lower row index, nearest first.  The search
+ *                is exact for every input (clustered, collinear, duplicated points, queries far outside the data).
+ *   outputs      K_S = amp k(X_S, X_S) + diag(yerr_S^2) (diagonal exactly amp + yerr^2), k* = amp k(X_S, x*_j), both evaluated on the
+ *                ORIGINAL coordinates by the evaluators of S1; L L^T = K_S, v = L^-1 k*, w = L^-1 y_S;
+ *                ys[j] = v . w;  var[j] = amp - v . v, not clamped (the convention of S3c).
+ *   failure      info[j] = 0, or the order of the first pivot that is not positive (NaN included); ys[j] and var[j] are then NaN
+ *                and every other query is unaffected, bit for bit.
+ *   independence a query's outputs depend on the training set, the kernel, kn and its own coordinates only: not on m, not on its
+ *                place in Xs, not on the other queries, not on the chunking.
+ * yerr may be NULL (no noise); var and nbr may be NULL.  nbr is (m, kn) row-major: S(j), original row indices; with kn > n the
+ * entries from n on are -1.  info (m) must not be NULL.
+ * On the device: a uniform grid over the bounding box of the whitened training points (mean occupancy of the order of kn / 4,
+ * one cell along an axis of zero extent), rows sorted by cell with a counting sort on the host; one search launch (one query per
+ * 64-lane workgroup: square rings of cells, the kn best in LDS, candidates merged by a bitonic sort, no bound on the number of
+ * candidates) and one solve launch (one query per workgroup: K_S, k* and y_S in one LDS matrix of kn + 2 rows, factorised with
+ * the right-hand sides carried along) per chunk of queries.  Chunks of 65 536 queries, TGP_LOCAL_CHUNK overrides; the bits do
+ * not depend on the chunk.  Memory is O(n + chunk kn) in the context's workspace, checked against the free device memory
+ * before anything runs (-2 with a message naming the bytes).
+ * Returns 0 when every query was attempted; -1 with a message for a NULL pointer (ctx, k, X, y, Xs, ys, info), n < 1 or
+ * n >= 2^31, m < 1, kn outside 1 .. 128, an unknown kind or an invLam without a Cholesky factor; -2 for HIP errors.
+ * Timings: [0] grid build and upload (host wall clock), [2] neighbour search, [3] local solves, device time summed over the
+ * chunks; every other slot 0.                                                                                                   */
+int tgp_gp_predict_local(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n, const double *y, const double *yerr,
+                         const double *Xs, int64_t m, int kn, double *ys, double *var, int32_t *nbr, int32_t *info);
 
 /* ---- S3b: cov (m, m) = k(Xs,Xs) - HT K^-1 HT^T using a kept factor ------------------------*/
 int tgp_gp_predict_cov(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X,

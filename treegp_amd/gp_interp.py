@@ -254,6 +254,36 @@ class GPInterpolation(object):
         ndim = 1 if np.ndim(X) < 2 else np.shape(X)[1]
         return ops.gp_predict_grad(spec, self._X, self._alpha, X)[:, :ndim]
 
+    def predict_local(self, X, k=64, return_var=False, return_neighbors=False):
+        """Local kriging at X (n_samples, 1 or 2): every point is predicted from its ``k`` nearest stars alone -- nearest in the
+        kernel's own metric -- instead of from one dense factorisation of all of them (ops.gp_predict_local, seam S3l of
+        include/tgp.h).  Not in the reference.  Linear in the number of points, no n x n matrix: with the 2-point-correlation
+        optimisers (which need no factorisation either) ``initialize`` -> ``solve`` -> ``predict_local`` serves catalogues of
+        10^5 - 10^6 stars that ``predict`` cannot hold.  Residual, ``_mean`` and the mean function are handled exactly as in
+        ``predict``: the GP acts on y - _mean - mean function and both are added back.  ``k`` in 1 .. 128, clipped to the number of
+        stars; with ``k`` >= that number the result is the exact GP's.  ``return_var``: also the variance of each local problem
+        (not clamped at zero; it is never below the exact GP's, which conditions on more).  ``return_neighbors``: also the
+        (n_samples, min(k, n)) rows of the stars used, nearest first.  ``_alpha`` and a kept factor are neither used nor
+        touched.  Raises numpy.linalg.LinAlgError naming the first point whose local matrix is not positive definite, and
+        NotImplementedError for 3-D coordinates, sums of kernels and the kernels of the dense route.  Runs on one GPU whichever
+        backend is set."""
+        if _three_d(self._X) or _three_d(X):
+            raise NotImplementedError("predict_local takes 1-D or 2-D coordinates: the neighbour search has no 3-D form")
+        try:
+            spec = _kernels.device_spec(self.kernel, single=kernel_to_spec)
+        except NotImplementedError:
+            raise NotImplementedError("predict_local needs one kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
+                                      "AnisotropicVonKarman, optionally times a constant); %r takes the dense route" % (self.kernel,))
+        if isinstance(spec, ops.KernelSumSpec):
+            raise NotImplementedError("predict_local takes one parametrised kernel: a sum of kernels has no single metric to rank "
+                                      "neighbours by; got %r" % (self.kernel,))
+        out = ops.gp_predict_local(spec, self._X, self._residual(), self._y_err, X, k=k, return_var=return_var,
+                                   return_neighbors=return_neighbors)
+        shift = self._mean + self._build_average_meanify(X)
+        if return_var or return_neighbors:
+            return (out[0] + shift,) + tuple(out[1:])
+        return out + shift
+
     def sample_y(self, X, n_samples=1, random_state=0, nugget=1e-10):
         """Realisations of the posterior at X (n_points, 1 or 2): (n_points, n_samples), scikit-learn's ``sample_y``
         layout (not in the reference).  y_star + L* z with y_star, cov = ``predict(X, return_cov=True)`` (mean, meanify and

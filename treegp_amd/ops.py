@@ -680,6 +680,59 @@ def gp_predict_grad(spec, X, alpha, Xs, ctx=None):
     return gs
 
 
+LOCAL_KMAX = 128
+
+
+def gp_predict_local(spec, X, y, y_err, Xs, k=64, return_var=False, return_neighbors=False, ctx=None):
+    """Local kriging (tgp_gp_predict_local, seam S3l of include/tgp.h): each query is conditioned on its ``k`` nearest training
+    points alone -- nearest in the kernel's own metric, ties to the lower row -- and gets the GP mean ``ys`` (and, for
+    ``return_var``, the variance ``amp - v.v``, not clamped) of that small problem.  No n x n matrix exists; the cost is linear
+    in the number of queries.  ``y`` is the residual the GP acts on, ``y_err`` its errors or None.  ``k`` in 1 .. 128 is
+    clipped to the number of training points (the result is then the exact GP's).  Returns ``ys``, then ``var`` if asked for,
+    then for ``return_neighbors`` the (m, min(k, n)) int32 rows of each query's neighbours, nearest first.  A query whose local
+    matrix is not positive definite raises numpy.linalg.LinAlgError naming the first one; the error carries ``info``
+    (per query: 0, or the order of the failing minor) and the outputs (NaN for failed queries) as ``.info`` and ``.results``.
+    ``spec`` is a 2-D ``KernelSpec``: a ``KernelSumSpec`` or a ``KernelSpec3`` raises NotImplementedError.  Runs on this
+    process's GPU whatever the multi-GPU settings."""
+    if isinstance(spec, KernelSumSpec):
+        raise NotImplementedError("gp_predict_local takes one parametrised kernel: a sum of kernels (KernelSumSpec) has no single "
+                                  "metric to rank neighbours by")
+    if isinstance(spec, KernelSpec3):
+        raise NotImplementedError("gp_predict_local takes 2-D coordinates: the bucket grid has no 3-D form (KernelSpec3)")
+    if not isinstance(spec, KernelSpec):
+        raise ValueError("gp_predict_local: spec must be a KernelSpec, got %r" % (type(spec).__name__,))
+    if int(k) != k or not 1 <= int(k) <= LOCAL_KMAX:
+        raise ValueError("gp_predict_local: k must be an integer in 1 .. %d, got %r" % (LOCAL_KMAX, k))
+    X2, Xs2 = as_xy(X), as_xy(Xs)
+    n, m = X2.shape[0], Xs2.shape[0]
+    y = f64(y).ravel()
+    if n < 1 or y.shape[0] != n:
+        raise ValueError("gp_predict_local: X holds %d points and y %d values" % (n, y.shape[0]))
+    e = None
+    if y_err is not None:
+        e = f64(y_err).ravel()
+        if e.shape[0] != n:
+            raise ValueError("gp_predict_local: X holds %d points and y_err %d values" % (n, e.shape[0]))
+    kn = min(int(k), n)
+    ys, var = np.empty(m), (np.empty(m) if return_var else None)
+    nbr = np.empty((m, kn), dtype=np.int32) if return_neighbors else None
+    info = np.zeros(m, dtype=np.int32)
+    if m > 0:
+        ctx = ctx or _lib.get_ctx()
+        lib = _lib.load_library()
+        rc = lib.tgp_gp_predict_local(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(y), ptr(e), ptr(Xs2), m, kn, ptr(ys), ptr(var),
+                                      ptr(nbr), ptr(info))
+        check(ctx, rc, "tgp_gp_predict_local")
+    out = (ys,) + ((var,) if return_var else ()) + ((nbr,) if return_neighbors else ())
+    bad = np.flatnonzero(info > 0)
+    if len(bad):
+        err = np.linalg.LinAlgError("gp_predict_local: query %d: the %d-th leading minor of its local matrix (k = %d) is not "
+                                    "positive definite (%d of %d queries failed)" % (bad[0], info[bad[0]], kn, len(bad), m))
+        err.info, err.results = info, out
+        raise err
+    return out if len(out) > 1 else ys
+
+
 def gp_predict_cov(spec, factor, X, Xs, ctx=None):
     """Posterior covariance k(Xs,Xs) - HT K^-1 HT^T (gp_interp.py:184-192) from a kept factor."""
     ctx = ctx or factor._ctx
