@@ -18,6 +18,7 @@
  *   S3e diag(K^-1) of a kept factor      not in the reference: leave-one-out residuals and variances (R&W 5.4.2)
  *   S3g gradient of HT @ alpha           not in the reference: d/dX2 of treegp/gp_interp.py:177,183 (kernels.py:114-126, 249-276, 355-381)
  *   S3l local kriging                    not in the reference: treegp/gp_interp.py:177-192 on each query's k nearest stars, no n x n factor
+ *   S3v local conditionals               not in the reference: S3l at the training rows themselves (leave-one-out, Vecchia's log L)
  *   S3f many small S3b / S3c at once    treegp/gp_interp.py:184-192 for the problems of S2e, README.rst:28
  *   S4  treecorr KKCorrelation.process   treegp/two_pcf.py:297-305, 330-334, 342-362
  *   S5  KNeighborsRegressor.predict      treegp/gp_interp.py:236-238
@@ -240,6 +241,42 @@ int tgp_gp_predict_grad(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int6
  * chunks; every other slot 0.                                                                                                   */
 int tgp_gp_predict_local(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n, const double *y, const double *yerr,
                          const double *Xs, int64_t m, int kn, double *ys, double *var, int32_t *nbr, int32_t *info);
+
+/* ---- S3v: local conditionals -- every TRAINING row conditioned on its kn nearest eligible rows: local leave-one-out, Vecchia -------
+ * Not in the reference.  The computation of S3l with the query x* = X[i] and a predicate on the candidate row in the search:
+ * what judges or fits a kernel (likelihood, held-out score) without the dense factor, linear in n.
+ * Definition.  k, X (2-D; 1-D as a zero second column), y, yerr, the metric, the whitening, d2 and the order of ties between
+ * eligible rows (to the lower row index), lists nearest first: exactly S3l's.  kn in 1 .. 128.
+ *   mode         TGP_LOCAL_LOO: the eligible rows of row i are all rows r != i -- by row index, not by coordinates: a duplicate
+ *                of point i at another row is a legal neighbour, the first one.
+ *                TGP_LOCAL_PRIOR: the rows with rank[r] < rank[i]; rank (n) must be a permutation of 0 .. n - 1, checked on the host
+ *                in O(n) (-1 with a message naming the first offending entry).  sum_i log N(y_i | mu_i, var_i + yerr_i^2) is then
+ *                Vecchia's approximation of log L, exact by the chain rule once kn reaches all predecessors.
+ *   S(i)         the min(kn, number of eligible rows) nearest eligible rows; cnt[i] its length (0 for the first row of the
+ *                ordering, or n = 1); the entries of nbr (n, kn) from cnt[i] on are -1.
+ *   nbr_in       not NULL: the lists are taken from it, (n, kn) with -1 padding at the end only; no search runs, mode and rank are
+ *                not consulted.  Checked on the host: every entry in [0, n) or a trailing -1, row i not in its own list (-1 with
+ *                a message naming the row).  A row repeated within a list is not looked for: it surfaces as info[i] > 0.
+ *   outputs      K_S, k* and the factorisation as in S3l with x* = X[i]: mu[i] = v . w, var[i] = amp - v . v (the LATENT variance,
+ *                not clamped); with cnt[i] = 0, mu = 0 and var = amp.  info[i] as in S3l; mu and var are NaN on failure and every
+ *                other row is unaffected, bit for bit.
+ *   sums[3]      sums[0] = sum log s2_i, sums[1] = sum (y_i - mu_i)^2 / s2_i over the rows with info = 0, s2_i = var[i] + yerr_i^2
+ *                (yerr^2 = 0 without yerr); sums[2] = the number of rows with info > 0.  The per-row terms are written to device
+ *                arrays and reduced by launches of their own after the last chunk, in a fixed tree over the row index (blocks of
+ *                1024: (e[t] + e[t+256]) + (e[t+512] + e[t+768]), a halving tree over t, then the same over the blocks): the bits
+ *                do not depend on TGP_LOCAL_CHUNK.  No atomics.
+ *   independence row i's outputs depend on the data, the kernel, kn, the mode or rank, and i only; not on the chunk.
+ *   identities   LOO: row i is tgp_gp_predict_local on the training set without row i, queried at X[i]; PRIOR: on the rows of lower
+ *                rank, kept in row order -- the same bits of mu and var, the same list after mapping the indices (the search is
+ *                exact, the solve is the same operations in the same order).
+ * mu, var, nbr, cnt and sums may each be NULL; info (n) must not be.  Memory is O(n + chunk kn), checked as in S3l (-2 with a
+ * message naming the bytes); -1 / -2 as in S3l, also -1 for a mode that is neither.  On -1 no output is written.
+ * Timings: [0] checks, grid build and upload (host wall clock), [2] neighbour search, [3] solves, terms and the reduction.      */
+#define TGP_LOCAL_LOO 0
+#define TGP_LOCAL_PRIOR 1
+int tgp_gp_local_cond(tgp_ctx *ctx, const tgp_kernel *k, const double *X, int64_t n, const double *y, const double *yerr,
+                      int mode, const int32_t *rank, int kn, const int32_t *nbr_in,
+                      double *mu, double *var, int32_t *nbr, int32_t *cnt, int32_t *info, double *sums);
 
 /* ---- S3b: cov (m, m) = k(Xs,Xs) - HT K^-1 HT^T using a kept factor ------------------------*/
 int tgp_gp_predict_cov(tgp_ctx *ctx, tgp_factor *f, const tgp_kernel *k, const double *X,

@@ -58,6 +58,8 @@ SIGNATURES = {
     "tgp_gp_predict_cov": (C.c_int, [_vp, _vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _i64, _vp]),
     # seam S3l: local kriging (ctx, k, X, n, y, yerr, Xs, m, kn, ys, var, nbr, info)
     "tgp_gp_predict_local": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, _vp, _i64, C.c_int, _vp, _vp, _vp, _vp]),
+    # seam S3v: local conditionals (ctx, k, X, n, y, yerr, mode, rank, kn, nbr_in, mu, var, nbr, cnt, info, sums)
+    "tgp_gp_local_cond": (C.c_int, [_vp, C.POINTER(TgpKernel), _vp, _i64, _vp, _vp, C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tgp_kk_twod": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp]),
     "tgp_kk_log": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tgp_kk_partial": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, _vp]),

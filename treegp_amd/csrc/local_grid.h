@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <vector>
 #include "../../include/tgp.h"
 
 // "Nearest" is measured on u = R x with R^T R = invLam (ARBF / AVK), R upper triangular: u0 = r00 x + r01 y, u1 = r11 y;
@@ -123,4 +124,43 @@ inline void local_grid_sort(const double *X, int64_t n, const LocalWhiten &R, co
     // now cell_start[c + 1] = start of cell c: shift down by one place and close with n
     for (int64_t c = 0; c < nc; ++c) cell_start[c] = cell_start[c + 1];
     cell_start[nc] = (int32_t)n;
+}
+
+// ---- seam S3v: the host checks of the local conditionals (tests/sanitize/local_cond_driver.cpp compiles them alone) ------------
+// rank (n) must be a permutation of 0 .. n - 1.  0 = it is; -1 = it is not, *bad = the first entry that is out of range or
+// repeats an earlier one.  O(n).
+inline int local_rank_check(const int32_t *rank, int64_t n, int64_t *bad) {
+    std::vector<char> seen((size_t)n, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t r = rank[i];
+        if (r < 0 || r >= n || seen[(size_t)r]) { *bad = i; return -1; }
+        seen[(size_t)r] = 1;
+    }
+    return 0;
+}
+
+// the ranks in the sorted-by-cell order of U: the search reads them beside the coordinates, not through perm
+inline void local_rank_sorted(const int32_t *rank, const int32_t *perm, int64_t n, int32_t *rank_s) {
+    for (int64_t s = 0; s < n; ++s) rank_s[s] = rank[perm[s]];
+}
+
+// Given lists nbr (rows [i0, i1) of an (n, kn) table): every entry a row of [0, n) other than the list's own, or a -1 of the
+// padding that closes the list.  cnt[i - i0] = the length of list i.  0 = ok; otherwise *bad_row = the first bad list, *bad_at its
+// first bad entry, and the return says why: -1 an entry outside [0, n), -2 the row itself, -3 an entry after a -1.
+// A row repeated within a list is not looked for: its matrix is singular and the solve reports it.
+inline int local_list_check(const int32_t *nbr, int64_t n, int kn, int64_t i0, int64_t i1, int32_t *cnt, int64_t *bad_row, int *bad_at) {
+    for (int64_t i = i0; i < i1; ++i) {
+        const int32_t *row = nbr + i * kn;
+        int len = 0;
+        while (len < kn && row[len] != -1) {
+            const int64_t v = row[len];
+            if (v < 0 || v >= n || v == i) { *bad_row = i; *bad_at = len; return v == i ? -2 : -1; }
+            ++len;
+        }
+        for (int t = len; t < kn; ++t) {
+            if (row[t] != -1) { *bad_row = i; *bad_at = t; return -3; }
+        }
+        cnt[i - i0] = len;
+    }
+    return 0;
 }

@@ -31,7 +31,9 @@ class GPInterpolation(object):
     statistics and raise ValueError for them.
 
     :param kernel:        string that ``eval_kernel`` turns into a scikit-learn kernel. [default 'RBF(1)']
-    :param optimizer:     "none", "two-pcf", "anisotropic" or "log-likelihood".
+    :param optimizer:     "none", "two-pcf", "anisotropic", "log-likelihood" or "local-likelihood" (not in the reference:
+                          L-BFGS-B on Vecchia's approximation of the likelihood, ``local_likelihood.py``; linear in n, no
+                          n x n factor; 1-D / 2-D coordinates and one parametrised kernel).
     :param normalize:     subtract the mean of the data before interpolating. [default True]
     :param p0:            start point (size, g1, g2) of the anisotropic 2-pcf fit.
     :param white_noise:   extra uncorrelated noise added in quadrature to y_err. [default 0.]
@@ -39,6 +41,8 @@ class GPInterpolation(object):
     :param average_fits:  FITS table (meanify output) holding the mean function. [default None]
     :param indice_meanify: column of the mean function to use when it has several.
     :param nbins, min_sep, max_sep: binning of the 2-point correlation function.
+    :param local_k, local_seed: neighbours per row and seed of the random ordering of "local-likelihood"; the other
+                          optimisers do not look at them. [default 64, 0]
     :param backend:       not in the reference.  None: one GPU, unless the multi-GPU route is enabled
                           (``treegp_amd.dist.enable()`` or TGP_DIST=1 under ``torchrun``) and the problem is at least its
                           size threshold; "dist": always the multi-GPU route (row-block-cyclic Cholesky over the ranks of
@@ -48,13 +52,14 @@ class GPInterpolation(object):
 
     def __init__(self, kernel="RBF(1)", optimizer="two-pcf", normalize=True, p0=[3000.0, 0.0, 0.0],
                  white_noise=0.0, n_neighbors=4, average_fits=None, indice_meanify=None, nbins=20,
-                 min_sep=None, max_sep=None, backend=None):
+                 min_sep=None, max_sep=None, backend=None, local_k=64, local_seed=0):
         if backend not in (None, "dist", "single"):
             raise ValueError("backend must be None, 'dist' or 'single'. Current value: %s" % (backend,))
         self.backend = backend
         self.normalize, self.optimizer, self.white_noise = normalize, optimizer, white_noise
         self.n_neighbors, self.indice_meanify = n_neighbors, indice_meanify
         self.nbins, self.min_sep, self.max_sep = nbins, min_sep, max_sep
+        self.local_k, self.local_seed = local_k, local_seed
         self.robust_fit = optimizer == "anisotropic"       # the 2-D fit of (size, g1, g2) goes with the TwoD pcf
         self.p0_robust_fit = p0
 
@@ -62,8 +67,8 @@ class GPInterpolation(object):
             raise TypeError("kernel should be a string a list or a numpy.ndarray of string")
         self.kernel_template = eval_kernel(kernel)
 
-        if optimizer not in ("anisotropic", "two-pcf", "log-likelihood", "none"):
-            raise ValueError("Only anisotropic, two-pcf, log-likelihood and none are supported for optimizer. "
+        if optimizer not in ("anisotropic", "two-pcf", "log-likelihood", "local-likelihood", "none"):
+            raise ValueError("Only anisotropic, two-pcf, log-likelihood, local-likelihood and none are supported for optimizer. "
                              "Current value: %s" % (optimizer))
 
         # mean function: the meanify table (gp_interp.py:97-107, read there with fitsio) or none yet
@@ -95,6 +100,9 @@ class GPInterpolation(object):
                                       robust_fit=self.robust_fit, p0=self.p0_robust_fit)
         elif self.optimizer == "log-likelihood":
             self._optimizer = log_likelihood(X, y, y_err)
+        elif self.optimizer == "local-likelihood":
+            from .local_likelihood import local_likelihood
+            self._optimizer = local_likelihood(X, y, y_err, k=self.local_k, seed=self.local_seed)
         else:
             return kernel
         return self._optimizer.optimizer(kernel)
@@ -387,6 +395,63 @@ class GPInterpolation(object):
                 raise
             total = -np.inf
         return total if np.isfinite(total) else -np.inf
+
+    # -- local leave-one-out and Vecchia's likelihood: no n x n factor (not in the reference) -----
+    def _local_spec(self, what, kernel=None):
+        """the 2-D ``KernelSpec`` of the kernel for the local routes, or their refusals in the style of ``predict_local``"""
+        return _kernels.local_spec(self.kernel if kernel is None else kernel, self._X, what, single=kernel_to_spec)
+
+    def predict_loo_local(self, k=64, return_var=False, return_neighbors=False):
+        """Local leave-one-out at the positions given to ``initialize``: entry i is predicted from the ``k`` nearest OTHER stars
+        alone -- nearest in the kernel's own metric; a duplicate of star i at another row is a legal neighbour -- with no n x n
+        factor (ops.gp_local_cond, seam S3v of include/tgp.h).  Linear in n: the held-out check of a fit on a catalogue that
+        ``predict_loo`` cannot hold, and the way to see on one's own data whether ``k`` is large enough.  Residual, ``_mean`` and
+        the mean function are handled as in ``predict_loo``; the variance of ``return_var`` is latent, as there, and not clamped.
+        With ``k`` >= n - 1 it is ``predict_loo``.  ``return_neighbors``: also the (n, k) rows used, nearest first, padded with -1,
+        and their lengths.  ``_alpha`` and a kept factor are neither used nor touched.  Raises numpy.linalg.LinAlgError naming the
+        first row whose local matrix is not positive definite, NotImplementedError for 3-D coordinates, sums of kernels and the
+        kernels of the dense route.  Runs on one GPU whichever backend is set."""
+        spec = self._local_spec("predict_loo_local")
+        out = ops.gp_local_cond(spec, self._X, self._residual(), self._y_err, k=k, mode="loo", return_neighbors=return_neighbors)
+        y_loo = out[0] + self._mean + self._spatial_average
+        res = (y_loo,) + ((out[1],) if return_var else ()) + (tuple(out[3:]) if return_neighbors else ())
+        return res if len(res) > 1 else y_loo
+
+    def _local_log_score(self, what, theta, k, mode, rank=None, neighbors=None):
+        """-1/2 sums[1] - 1/2 sums[0] - n/2 log 2 pi of ops.gp_local_cond; -inf when a row failed (as ``log_likelihood``)"""
+        from ._lib import TgpError
+        from .log_likelihood import _rejects_theta
+        kernel = copy.deepcopy(self.kernel)
+        if theta is not None:
+            kernel = kernel.clone_with_theta(theta)
+        spec = self._local_spec(what, kernel)
+        try:
+            _, _, sums = ops.gp_local_cond(spec, self._X, self._residual(), self._y_err, k=k, mode=mode, rank=rank,
+                                           neighbors=neighbors)
+            total = -0.5 * sums[1] - 0.5 * sums[0] - 0.5 * len(self._X) * np.log(2.0 * np.pi)
+        except (np.linalg.LinAlgError, FloatingPointError):
+            total = -np.inf
+        except TgpError as ex:
+            # an invLam without a Cholesky factor is a rejected theta, as a K that is not positive definite is
+            if "has no Cholesky factor" not in str(ex) and not _rejects_theta(ex):
+                raise
+            total = -np.inf
+        return float(total) if np.isfinite(total) else -np.inf
+
+    def return_loo_log_predictive_local(self, theta=None, k=64):
+        """sum_i log N(y_i | mu_i, var_i + y_err_i^2) with mu_i, var_i the local leave-one-out of ``predict_loo_local`` for the
+        current (or the given) hyper-parameters: ``return_loo_log_predictive`` without the dense factor, the same number when
+        ``k`` >= n - 1.  A held-out score to compare two fits of a large catalogue with.  -inf when a local matrix is not positive
+        definite."""
+        return self._local_log_score("return_loo_log_predictive_local", theta, k, "loo")
+
+    def return_log_likelihood_local(self, theta=None, k=64, seed=0):
+        """Vecchia's approximation of the log-likelihood for the current (or the given) hyper-parameters:
+        sum_i log N(y_i | mu_i, var_i + y_err_i^2), row i conditioned on its ``k`` nearest rows among those earlier in the random
+        ordering ``ops.vecchia_rank(n, seed)``.  By the chain rule it is ``return_log_likelihood`` when ``k`` >= n - 1; it is
+        linear in n and needs no n x n factor.  -inf when any row's local matrix is not positive definite, as ``log_likelihood``
+        returns for K."""
+        return self._local_log_score("return_log_likelihood_local", theta, k, "prior", rank=ops.vecchia_rank(len(self._X), seed))
 
     # -- error bars on the hyper-parameters (not in the reference) --------------------------------
     def return_fisher_information(self, theta=None):

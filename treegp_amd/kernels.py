@@ -339,6 +339,23 @@ def device_spec(kernel, allow_sum=True, single=None, ndim=2):
         return kernel_to_sum_spec(kernel)
 
 
+def local_spec(kernel, X, what, single=None):
+    """The 2-D ``ops.KernelSpec`` of ``kernel`` for the routes of the local conditionals (``GPInterpolation.predict_loo_local``
+    and its scores, ``optimizer="local-likelihood"``), or their refusals, in the style of ``predict_local``'s: NotImplementedError
+    naming ``what`` for 3-D coordinates ``X``, for the kernel trees of the dense route and for sums of kernels."""
+    if np.ndim(X) == 2 and np.shape(X)[1] == 3:
+        raise NotImplementedError("%s takes 1-D or 2-D coordinates: the neighbour search has no 3-D form" % what)
+    try:
+        spec = device_spec(kernel, single=single or kernel_to_spec)
+    except NotImplementedError:
+        raise NotImplementedError("%s needs one kernel with a device form (RBF, AnisotropicRBF, VonKarman, "
+                                  "AnisotropicVonKarman, optionally times a constant); %r takes the dense route" % (what, kernel))
+    if isinstance(spec, ops.KernelSumSpec):
+        raise NotImplementedError("%s takes one parametrised kernel: a sum of kernels has no single metric to rank "
+                                  "neighbours by; got %r" % (what, kernel))
+    return spec
+
+
 def sum_spec_jacobian(kernel):
     """d(log amp_t, a_t, b_t, c_t for every term t) / d theta, shape (ntheta, 4 * nterms), for the sums ``kernel_to_sum_spec``
     accepts: block structured, the theta of a Sum being k1.theta then k2.theta, term t's rows ``spec_jacobian(term_t,

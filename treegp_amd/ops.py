@@ -733,6 +733,85 @@ def gp_predict_local(spec, X, y, y_err, Xs, k=64, return_var=False, return_neigh
     return out if len(out) > 1 else ys
 
 
+LOCAL_MODES = {"loo": 0, "prior": 1}       # TGP_LOCAL_LOO, TGP_LOCAL_PRIOR
+
+
+def vecchia_rank(n, seed=0):
+    """The rank array (int32, a permutation of 0 .. n - 1) of the ordering ``np.random.default_rng(seed).permutation(n)``: row
+    ``permutation[j]`` has rank j.  The default ordering of the Vecchia likelihood (``gp_local_cond(mode="prior")``): the literature
+    on Vecchia orderings reports a random ordering close to max-min ordering and clearly better than sorting by a coordinate."""
+    order = np.random.default_rng(seed).permutation(int(n))
+    rank = np.empty(int(n), dtype=np.int32)
+    rank[order] = np.arange(int(n), dtype=np.int32)
+    return rank
+
+
+def gp_local_cond(spec, X, y, y_err, k=64, mode="loo", rank=None, neighbors=None, return_neighbors=False, ctx=None):
+    """Local conditionals (tgp_gp_local_cond, seam S3v of include/tgp.h): every TRAINING row i gets the mean ``mu[i]`` and the latent
+    variance ``var[i]`` (``amp - v.v``, not clamped) of the GP conditioned on its ``k`` nearest eligible rows alone, by the search and
+    the solve of ``gp_predict_local``.  ``mode="loo"``: every other row is eligible (local leave-one-out).  ``mode="prior"``: the
+    rows of lower ``rank`` (an int permutation of 0 .. n - 1, required; ``vecchia_rank`` makes one), and
+    ``-0.5 sums[1] - 0.5 sums[0] - n/2 log 2 pi`` is Vecchia's approximation of the log-likelihood, the exact one when ``k`` reaches
+    all predecessors.  ``neighbors``: (n, k) int32 lists with -1 padding at the end only, used instead of a search (``mode`` and
+    ``rank`` are then not consulted): a fit finds them once and keeps them, so that its objective is smooth in theta.
+    ``y`` is the residual the GP acts on, ``y_err`` its errors or None.  ``k`` in 1 .. 128 is not clipped: lists are padded with -1.
+    Returns ``(mu, var, sums)`` -- sums = [sum log s2_i, sum (y_i - mu_i)^2 / s2_i over the rows that did not fail, number of failed
+    rows], s2_i = var_i + y_err_i^2, reduced on the device in a fixed order -- then for ``return_neighbors`` ``(nbr, cnt)``: the
+    (n, k) lists, nearest first, and their lengths.  A row whose local matrix is not positive definite raises
+    numpy.linalg.LinAlgError naming the first one; the error carries ``.info`` and ``.results`` (the outputs, NaN for failed rows).
+    ``spec`` is a 2-D ``KernelSpec``: a ``KernelSumSpec`` or a ``KernelSpec3`` raises NotImplementedError.  Runs on this process's
+    GPU whatever the multi-GPU settings."""
+    if isinstance(spec, KernelSumSpec):
+        raise NotImplementedError("gp_local_cond takes one parametrised kernel: a sum of kernels (KernelSumSpec) has no single "
+                                  "metric to rank neighbours by")
+    if isinstance(spec, KernelSpec3):
+        raise NotImplementedError("gp_local_cond takes 2-D coordinates: the bucket grid has no 3-D form (KernelSpec3)")
+    if not isinstance(spec, KernelSpec):
+        raise ValueError("gp_local_cond: spec must be a KernelSpec, got %r" % (type(spec).__name__,))
+    if int(k) != k or not 1 <= int(k) <= LOCAL_KMAX:
+        raise ValueError("gp_local_cond: k must be an integer in 1 .. %d, got %r" % (LOCAL_KMAX, k))
+    if mode not in LOCAL_MODES:
+        raise ValueError("gp_local_cond: mode must be 'loo' or 'prior', got %r" % (mode,))
+    X2 = as_xy(X)
+    n, kn = X2.shape[0], int(k)
+    y = f64(y).ravel()
+    if n < 1 or y.shape[0] != n:
+        raise ValueError("gp_local_cond: X holds %d points and y %d values" % (n, y.shape[0]))
+    e = None
+    if y_err is not None:
+        e = f64(y_err).ravel()
+        if e.shape[0] != n:
+            raise ValueError("gp_local_cond: X holds %d points and y_err %d values" % (n, e.shape[0]))
+    nbr_in = r32 = None
+    if neighbors is not None:
+        nbr_in = np.ascontiguousarray(neighbors, dtype=np.int32)
+        if nbr_in.shape != (n, kn):
+            raise ValueError("gp_local_cond: neighbors must be (%d, %d), got %r" % (n, kn, nbr_in.shape))
+    elif mode == "prior":
+        if rank is None:
+            raise ValueError("gp_local_cond: mode='prior' needs rank, a permutation of 0 .. n - 1 (ops.vecchia_rank)")
+        r32 = np.ascontiguousarray(rank, dtype=np.int32).ravel()
+        if r32.shape[0] != n:
+            raise ValueError("gp_local_cond: X holds %d points and rank %d values" % (n, r32.shape[0]))
+    mu, var, sums = np.empty(n), np.empty(n), np.zeros(3)
+    nbr = np.empty((n, kn), dtype=np.int32) if return_neighbors else None
+    cnt = np.empty(n, dtype=np.int32) if return_neighbors else None
+    info = np.zeros(n, dtype=np.int32)
+    ctx = ctx or _lib.get_ctx()
+    lib = _lib.load_library()
+    rc = lib.tgp_gp_local_cond(ctx, C.byref(spec.to_c()), ptr(X2), n, ptr(y), ptr(e), LOCAL_MODES[mode], ptr(r32), kn, ptr(nbr_in),
+                               ptr(mu), ptr(var), ptr(nbr), ptr(cnt), ptr(info), ptr(sums))
+    check(ctx, rc, "tgp_gp_local_cond")
+    out = (mu, var, sums) + ((nbr, cnt) if return_neighbors else ())
+    bad = np.flatnonzero(info > 0)
+    if len(bad):
+        err = np.linalg.LinAlgError("gp_local_cond: row %d: the %d-th leading minor of its local matrix (k = %d) is not positive "
+                                    "definite (%d of %d rows failed)" % (bad[0], info[bad[0]], kn, len(bad), n))
+        err.info, err.results = info, out
+        raise err
+    return out
+
+
 def gp_predict_cov(spec, factor, X, Xs, ctx=None):
     """Posterior covariance k(Xs,Xs) - HT K^-1 HT^T (gp_interp.py:184-192) from a kept factor."""
     ctx = ctx or factor._ctx
