@@ -107,6 +107,19 @@ def log_score_ld(y, y_err, mu, var):
     return -LD(0.5) * t1.sum() - LD(0.5) * t0.sum() - LD(0.5) * len(y) * LOG_2PI
 
 
+def check_sums(y, y_err, mu, var, sums, tag=""):
+    """sums against the long-double sums of the terms formed from the device's own mu and var: (log2 n + 8) 2^-53 sum |t_i| --
+    the fixed tree, and the few-ulp log and the divide of each term"""
+    t0, t1, _, _ = terms_ld(y, y_err, mu, var)
+    n = len(y)
+    for j, t in enumerate((t0, t1)):
+        bound = (np.log2(n) + 8.0) * 2.0 ** -53 * float(np.abs(t).sum())
+        err = abs(float(LD(sums[j]) - t.sum()))
+        print("%s sums[%d]: |device - long double| = %.3e, bound %.3e" % (tag, j, err, bound))
+        assert err <= bound
+    assert sums[2] == 0.0
+
+
 def dense_loglik_ld(K, y, y_err):
     """log L of the dense GP in np.longdouble: K float64 with diagonal amp; returns (log L, y.K^-1.y, log det)"""
     n = len(y)

@@ -64,17 +64,7 @@ def value_errors(spec, X, y, y_err, mu, var, nbr, cnt, K=None):
     return np.abs(mu - r_mu).max() / np.abs(y).max(), np.abs(var - r_var).max() / spec.amp, r_mu, r_var
 
 
-def check_sums(y, y_err, mu, var, sums, tag=""):
-    """sums against the long-double sums of the terms formed from the device's own mu and var: (log2 n + 8) 2^-53 sum |t_i| --
-    the fixed tree, and the few-ulp log and the divide of each term"""
-    t0, t1, _, _ = VR.terms_ld(y, y_err, mu, var)
-    n = len(y)
-    for j, t in enumerate((t0, t1)):
-        bound = (np.log2(n) + 8.0) * 2.0 ** -53 * float(np.abs(t).sum())
-        err = abs(float(LD(sums[j]) - t.sum()))
-        print("%s sums[%d]: |device - long double| = %.3e, bound %.3e" % (tag, j, err, bound))
-        assert err <= bound
-    assert sums[2] == 0.0
+check_sums = VR.check_sums
 
 
 # ---------------------------------------------------------------------------------------------------------
