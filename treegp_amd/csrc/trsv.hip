@@ -150,7 +150,9 @@ __global__ __launch_bounds__(1024) void logdet_dot_kernel(const double *__restri
 // The right-hand side as one more row of the matrix: row Np-1 (a padding row, n < Np) <- [y (n), 0 ..., 1e300].  The
 // factorisation then leaves L^-1 y in that row -- the panel solves and updates treat it like any other row below the
 // diagonal -- and a likelihood evaluation needs no triangular sweep at all.  The huge diagonal keeps the row's own pivot
-// positive whatever |L^-1 y|^2 is; nothing lies below or to the right of it, and the log-determinant stops at row n.
+// positive as long as |L^-1 y|^2 = y^T (K + D)^-1 y stays below 1e300: the one constant on this path that carries a unit, that
+// of y^2 / amp, and so the range this route represents (DESIGN.md "Units"; tests/test_gpu_units.py holds the route to equal
+// bits for y scaled by 2^-40 .. 2^40).  Nothing lies below or to the right of it, and the log-determinant stops at row n.
 __global__ void augment_rhs_kernel(double *__restrict__ A, int64_t Np, int64_t n, const double *__restrict__ y) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (c >= Np) return;
